@@ -11,6 +11,8 @@ independent streams (weak scaling, no collective on the data path).
 
   python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: starts its own N ranks)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py ... --full                 (also the event-timed, single-queue, device-copy and CPU-baseline legs)
+  python bench.py ... --dump-outputs DIR     (the last timed step's output, sampled, as DIR/*.npy)
 
 Prints ONE JSON line on rank 0.
 """
@@ -51,6 +53,19 @@ def lowpass_taps(ntaps=NTAPS, cutoff=0.25):
     w = 0.54 - 0.46 * np.cos(2 * np.pi * k / (ntaps - 1))
     t = sinc * w
     return (t / t.sum()).astype(np.complex64)
+
+
+DUMP_SEED, DUMP_DRAWS = 815, 1 << 21
+
+
+def dump_outputs(out_dir, y):
+    """--dump-outputs: the last timed step's output stream (16 Mi cf32 = 128 MiB, over the size limit) as a fixed
+    seeded sample: fir_out.npy = float32 [n, 2] (re, im) at the ascending stream positions of fir_out_index.npy
+    (float64, exact below 2^53); n ~ 1.9 Mi, ~30 MiB in all.  The same positions in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, y.size, DUMP_DRAWS))
+    np.save(os.path.join(out_dir, "fir_out.npy"), np.ascontiguousarray(y[idx]).view(np.float32).reshape(-1, 2))
+    np.save(os.path.join(out_dir, "fir_out_index.npy"), idx.astype(np.float64))
 
 
 def cpu_model():
@@ -465,6 +480,14 @@ def main():
                      help="untimed launches of the same step before the warm-up so that the device has left its "
                           "load-onset power transient (tools/transient.py: ~25 ms after any idle gap >= 5 ms)")
     ap_.add_argument("--streams", type=int, default=6, help="rotating working set, x 256 MiB (in+out) each")
+    ap_.add_argument("--full", action="store_true",
+                     help="after the headline's timed region, run the legs beyond it as well: the same steps again "
+                          "between HIP events, the steps on one queue (--no-single-queue-leg skips it), a device copy "
+                          "of the same bytes, the committed HBM traffic profile and the CPU baseline (--no-cpu-baseline "
+                          "skips it).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap_.add_argument("--dump-outputs", metavar="DIR", default=None,
+                     help="write what the last timed step computed to DIR/<name>.npy (headline workload, rank 0): "
+                          "a fixed seeded sample of its output stream, see dump_outputs()")
     ap_.add_argument("--no-cpu-baseline", action="store_true")
     ap_.add_argument("--no-overlap", action="store_true",
                      help="run the timed region on ONE HIP queue (aeth_ctx_set_overlap off): every launch then waits for "
@@ -480,6 +503,10 @@ def main():
     ap_.add_argument("--workload", default="c3", choices=["c3", "c2", "c4", "c5", "criterion"],
                      help="c3 (default) = the headline config; the others are BASELINE configs 2, 4, 5 for the record")
     args = ap_.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap_.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "c3":
+        ap_.error("--dump-outputs writes the headline workload's outputs (--workload c3)")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args))
     if args.workload == "criterion":
@@ -546,41 +573,46 @@ def main():
     # sync | exactly K steps | sync + barrier, wall time, MAX over ranks.  Nothing but the K launches is enqueued inside.
     elapsed, _ = timed(args.steps, args.warmup)
     elapsed = ranks.max_over_ranks(elapsed)
-    # The same K steps again with HIP events recorded around them on the context's stream (behind both queues):
-    # `roofline.frac_events`, the device-side view of the same region without the host's launch and wake-up latency.
-    for i in range(args.warmup):
-        step(i)
-    _, ev_ms = timed(args.steps, args.warmup, events=True)
-    step_ms = ev_ms / max(args.steps, 1)
+    # the last timed step's output, before anything below writes the output buffers again
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[(args.warmup + args.steps - 1) % nstreams].to_host())
 
-    # Extra leg (rank 0's GPU, untimed for `value`): the same steps on ONE queue.  Per-launch kernel time as
-    # rocprofv3 --kernel-trace sees it (profiles/): with two queues the dispatches overlap and their individual
-    # durations no longer add up to the wall time.
-    single = None
-    if overlap and not args.no_single_queue_leg:
-        ctx.set_overlap(False)
-        for i in range(max(args.warmup, 5)):
+    step_ms = single = copy_gbs = None
+    if args.full:
+        # The same K steps again with HIP events recorded around them on the context's stream (behind both queues):
+        # `roofline.frac_events`, the device-side view of the same region without the host's launch and wake-up latency.
+        for i in range(args.warmup):
             step(i)
-        w1, e1 = timed(args.steps, args.warmup, events=True)
-        ctx.set_overlap(True)
-        k_ms = e1 / max(args.steps, 1)
-        single = {"queues": 1, "kernel_ms": round(k_ms, 5),
-                  "value": round(float(STREAM) * args.steps / w1 / 1e9, 3), "unit": "GSamples/s",
-                  "achieved_GBps": round(BYTES_PER_SAMPLE * STREAM / (k_ms * 1e-3) / 1e9, 1),
-                  "frac": round(BYTES_PER_SAMPLE * STREAM / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                  "note": "one launch at a time: fill + drain of every launch exposed; this is the duration a "
-                          "kernel trace reports per dispatch"}
-    barrier()
-    # a plain device copy of the same bytes, same buffers, right behind the timed region (the
-    # fraction is reported against the spec peak AND against what a copy reaches on this device)
-    c0, c1 = ctx.event(), ctx.event()
-    for i in range(20):
-        outs[i % nstreams].vec_clone(ins[i % nstreams])
-    c0.record()
-    for i in range(200):
-        outs[i % nstreams].vec_clone(ins[i % nstreams])
-    c1.record(); ctx.sync()
-    copy_gbs = BYTES_PER_SAMPLE * STREAM / (c0.elapsed_ms(c1) / 200 * 1e-3) / 1e9
+        _, ev_ms = timed(args.steps, args.warmup, events=True)
+        step_ms = ev_ms / max(args.steps, 1)
+
+        # Extra leg (rank 0's GPU, untimed for `value`): the same steps on ONE queue.  Per-launch kernel time as
+        # rocprofv3 --kernel-trace sees it (profiles/): with two queues the dispatches overlap and their individual
+        # durations no longer add up to the wall time.
+        if overlap and not args.no_single_queue_leg:
+            ctx.set_overlap(False)
+            for i in range(max(args.warmup, 5)):
+                step(i)
+            w1, e1 = timed(args.steps, args.warmup, events=True)
+            ctx.set_overlap(True)
+            k_ms = e1 / max(args.steps, 1)
+            single = {"queues": 1, "kernel_ms": round(k_ms, 5),
+                      "value": round(float(STREAM) * args.steps / w1 / 1e9, 3), "unit": "GSamples/s",
+                      "achieved_GBps": round(BYTES_PER_SAMPLE * STREAM / (k_ms * 1e-3) / 1e9, 1),
+                      "frac": round(BYTES_PER_SAMPLE * STREAM / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                      "note": "one launch at a time: fill + drain of every launch exposed; this is the duration a "
+                              "kernel trace reports per dispatch"}
+        barrier()
+        # a plain device copy of the same bytes, same buffers, right behind the timed region (the
+        # fraction is reported against the spec peak AND against what a copy reaches on this device)
+        c0, c1 = ctx.event(), ctx.event()
+        for i in range(20):
+            outs[i % nstreams].vec_clone(ins[i % nstreams])
+        c0.record()
+        for i in range(200):
+            outs[i % nstreams].vec_clone(ins[i % nstreams])
+        c1.record(); ctx.sync()
+        copy_gbs = BYTES_PER_SAMPLE * STREAM / (c0.elapsed_ms(c1) / 200 * 1e-3) / 1e9
 
     if rank == 0:
         assert seen == args.gpus, f"collective spans {seen} ranks, --gpus says {args.gpus}"
@@ -588,8 +620,6 @@ def main():
         value = total_samples / elapsed / 1e9
         # per GPU, from the SAME clock as `value`: algorithmic bytes of one launch / (wall time of the region / K)
         achieved = BYTES_PER_SAMPLE * STREAM / (elapsed / args.steps) / 1e9
-        achieved_ev = BYTES_PER_SAMPLE * STREAM / (step_ms * 1e-3) / 1e9
-        traffic = measured_traffic() or (None, None)
         line = {
             "metric": "GSamples/s cf32 (FFT-2048 + 64-tap FIR chain)",
             "value": round(value, 3), "unit": "GSamples/s", "n_gpus": seen, "steps": args.steps,
@@ -609,22 +639,26 @@ def main():
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "level": "step: algorithmic bytes of one launch / (wall time of the timed region / steps), per GPU" + (
-                             "; two launches overlap, see per_dispatch_* for the duration of one dispatch" if overlap else ""),
-                         "achieved_events": round(achieved_ev, 1), "frac_events": round(achieved_ev / HBM_PEAK_GBS, 4),
-                         "events_note": "the same K steps repeated with HIP events recorded around them on the context's "
-                                        "stream, behind both queues (device-side time: no host launch / wake-up latency)",
-                         "device_copy_GBps": round(copy_gbs, 1), "frac_of_device_copy": round(achieved / copy_gbs, 4),
-                         "traffic": traffic[1], "traffic_source": traffic[0],
-                         "kernel": "fmi_kernel<Cfg<2048,16,16,16,8>> (V_PRIO|V_XOR; +V_SPREAD for a launch that runs alone)", "step_ms_events": round(step_ms, 5),
+                             "; two launches overlap, see per_dispatch_* for the duration of one dispatch" if single is not None else ""),
+                         "kernel": "fmi_kernel<Cfg<2048,16,16,16,8>> (V_PRIO|V_XOR; +V_SPREAD for a launch that runs alone)",
                          "bytes_per_launch": BYTES_PER_SAMPLE * STREAM},
         }
+        if args.full:
+            achieved_ev = BYTES_PER_SAMPLE * STREAM / (step_ms * 1e-3) / 1e9
+            traffic = measured_traffic() or (None, None)
+            line["roofline"].update({
+                "achieved_events": round(achieved_ev, 1), "frac_events": round(achieved_ev / HBM_PEAK_GBS, 4),
+                "events_note": "the same K steps repeated with HIP events recorded around them on the context's "
+                               "stream, behind both queues (device-side time: no host launch / wake-up latency)",
+                "device_copy_GBps": round(copy_gbs, 1), "frac_of_device_copy": round(achieved / copy_gbs, 4),
+                "traffic": traffic[1], "traffic_source": traffic[0], "step_ms_events": round(step_ms, 5)})
         if single is not None:
             line["single_queue"] = single
             # the same kernel one dispatch at a time (what rocprofv3 --kernel-trace --stats averages): kept inside the
             # roofline object too, so that nobody reads the step-level fraction as a per-dispatch one
             line["roofline"]["per_dispatch_ms"] = single["kernel_ms"]
             line["roofline"]["per_dispatch_frac"] = single["frac"]
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
 

@@ -45,3 +45,12 @@ def test_rank_count_mismatch_is_an_error():
                        capture_output=True, text=True, env=env, timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE=1" in p.stderr
     assert not any(l.startswith("{") for l in p.stdout.splitlines())
+
+
+def test_bad_arguments_fail_before_any_gpu_call():
+    """--steps sets the number of timed steps, so a run without one is refused; --dump-outputs is the headline's."""
+    for extra in (["--steps", "0"], ["--warmup", "-1"], ["--workload", "c4", "--dump-outputs", "out"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *extra], capture_output=True, text=True,
+                           timeout=120)
+        assert p.returncode == 2 and "error" in p.stderr, (extra, p.stderr)
+        assert not any(l.startswith("{") for l in p.stdout.splitlines())

@@ -188,7 +188,10 @@ def test_a_huge_chunk_is_split_so_that_a_slot_stays_bounded(ctx, plan):
 
 
 def _free_bytes():
-    hip = C.CDLL("libamdhip64.so")
+    # hipMemGetInfo of the runtime libaether_hip.so is bound to (looked up through its handle): once torch is
+    # imported, the file name "libamdhip64.so" names the copy bundled with torch
+    from aether_primitives_amd import _lib
+    hip = _lib.load()
     free, total = C.c_size_t(0), C.c_size_t(0)
     assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
     return free.value

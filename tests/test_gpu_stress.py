@@ -101,7 +101,10 @@ def test_plans_release_their_device_memory(ctx, oracle):
     """create / run / destroy every kind of plan many times: free device memory returns to where it was"""
     import ctypes
     import gc
-    hip = ctypes.CDLL("libamdhip64.so")                      # the runtime libaether_hip.so already loaded
+    # the HIP runtime libaether_hip.so is bound to: symbols looked up through its handle (its dependency scope), not
+    # by file name -- once torch is imported, "libamdhip64.so" names the copy bundled with torch
+    from aether_primitives_amd import _lib
+    hip = _lib.load()
 
     def free_bytes():
         free, total = ctypes.c_size_t(), ctypes.c_size_t()

@@ -8,6 +8,8 @@ tests"; GPU sanitizers are not available on the pool).
 * the oracle's C restatement rebuilt with -fsanitize=address,undefined (`make -C oracle asan`) and run through the
   reference's known-answer tests (tests/test_oracle_golden.py) in a child interpreter."""
 import os
+import platform
+import shutil
 import subprocess
 import sys
 
@@ -19,6 +21,17 @@ INC = os.path.join(ROOT, "aether_primitives_amd", "csrc")
 OUT = os.path.join(ROOT, "tests", "cpp", "build")
 
 
+def _without_aslr():
+    """gcc's ThreadSanitizer keeps its shadow at fixed addresses and stops with "unexpected memory mapping" on hosts whose
+    mmap randomisation is wider than it was built for.  `setarch -R` runs the one binary with address randomisation
+    off (a personality flag of that process, nothing host-wide); [] where setarch is missing or the flag is refused."""
+    setarch = shutil.which("setarch")
+    if setarch is None:
+        return []
+    cmd = [setarch, platform.machine(), "-R"]
+    return cmd if subprocess.run(cmd + ["true"], capture_output=True).returncode == 0 else []
+
+
 @pytest.mark.parametrize("san", ["thread", "address,undefined"])
 def test_hostcore_under_sanitizer(san):
     os.makedirs(OUT, exist_ok=True)
@@ -27,7 +40,8 @@ def test_hostcore_under_sanitizer(san):
                            SRC, "-o", exe, "-lpthread"])
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1", ASAN_OPTIONS="detect_leaks=1",
                UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    p = subprocess.run((_without_aslr() if san == "thread" else []) + [exe], capture_output=True, text=True, timeout=300,
+                       env=env)
     assert p.returncode == 0 and "hostcore: ok" in p.stdout, p.stdout + p.stderr
     assert "WARNING: ThreadSanitizer" not in p.stderr and "ERROR: AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr
 
