@@ -75,7 +75,14 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
     // ... and N = 2048 (the configuration it was measured on) keeps its exchange image XOR-swizzled instead of padded:
     // no two-way conflict on the contiguous reads, transform-only time 39.8 -> 34.8 us, launch 54.8 -> 53.4 us
     constexpr int VAR = (C::F == 1) ? (V_PRIO | ((C::N == 2048 && C::P == 16) ? V_XOR : 0)) : 0;
-    if constexpr (C::F == 1) {
+    // the demodulating and decimating stores are built for the lengths the host routes to them, 1024 ... 4096
+    // (aeth_fft_mul_ifft_demod, aeth_fir_exec_decim); no other length carries a build of either
+    constexpr bool kStoreVariants = C::F == 1 && 1024 <= C::N && C::N <= 4096;
+    if constexpr (!kStoreVariants) {
+        if (b.bits || b.dec.d > 1)
+            return aeth::set_error(AETH_E_UNSUPPORTED, "fused FFT*H*IFFT: no demodulating / decimating build of length %d", C::N);
+    }
+    if constexpr (kStoreVariants) {
         if (b.bits) {                                       // hard demodulation instead of the sample store
             // the decision's mode is a template parameter (aeth_fir_kernel.h: demod_block): BPSK, QPSK with a
             // separable table, QPSK with any other table -- nothing about it is tested per sample
@@ -95,7 +102,7 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
             return AETH_OK;
         }
     }
-    if constexpr (C::F == 1 && !SCALED) {
+    if constexpr (kStoreVariants && !SCALED) {
         if (b.dec.d > 1) {                                  // decimating store (aeth_fir_exec_decim)
             // without the swizzle: with it the N = 2048 build needs 260 VGPRs and drops to one wave per SIMD (62 us
             // per 16 Mi-sample launch against 50)
