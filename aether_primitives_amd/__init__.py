@@ -12,7 +12,8 @@ from ._lib import AetherError, LengthMismatch, load as _load
 
 _load()   # fail loudly at import time if the HIP library is not built
 
-from .context import Context, DeviceVec, HostVec          # noqa: E402
+from .context import (Context, DeviceVec, DeviceF32, HostVec, VecStats,  # noqa: E402
+                      LEVEL_NORM, LEVEL_DB, LEVEL_POWER_DB)
 from .fft import Scale, HipFft, SIGN_REF_FWD, SIGN_REF_BWD  # noqa: E402
 from .fir import Fir                                      # noqa: E402
 from . import sampling                                    # noqa: E402
@@ -23,5 +24,6 @@ from . import pool                                        # noqa: E402
 from . import pipeline                                    # noqa: E402
 from .evm import assert_evm, evm_db                       # noqa: E402
 
-__all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "HostVec", "Scale", "HipFft",
+__all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "DeviceF32", "HostVec", "VecStats", "LEVEL_NORM",
+           "LEVEL_DB", "LEVEL_POWER_DB", "Scale", "HipFft",
            "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "sampling", "modulation", "noise", "assert_evm", "evm_db"]

@@ -130,6 +130,10 @@ PROTOTYPES = {
     "aeth_rng_philox4x32_10": (i32, [vp, vp, sz, vp]),
     "aeth_rng_philox4x32": (i32, [vp, vp, sz, i32, vp]),
     "aeth_rng_normal_pairs": (i32, [vp, vp, sz, vp]),
+    "aeth_vec_stats": (i32, [vp, vp, sz, vp]),
+    "aeth_host_vec_stats": (i32, [vp, vp, sz, vp]),
+    "aeth_vec_levels": (i32, [vp, vp, sz, i32, vp, sz]),
+    "aeth_fft_exec_levels": (i32, [vp, vp, sz, sz, i32, i32, f32, i32, i32, vp, sz]),
 }
 
 _lib = None

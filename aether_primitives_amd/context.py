@@ -19,6 +19,35 @@ def _c64(a):
     return a
 
 
+# level kinds of aeth_vec_levels / aeth_fft_exec_levels (include/aether_hip.h, AETH_LEVEL_*)
+LEVEL_NORM, LEVEL_DB, LEVEL_POWER_DB = 0, 1, 2
+
+
+class _VecStats(C.Structure):
+    # struct aeth_vec_stats
+    _fields_ = [("n", C.c_size_t), ("n_nan", C.c_size_t), ("min_index", C.c_size_t), ("max_index", C.c_size_t),
+                ("min_norm", C.c_float), ("max_norm", C.c_float), ("mean_re", C.c_double), ("mean_im", C.c_double),
+                ("power", C.c_double)]
+
+
+class VecStats:
+    """What `stats()` returns (the reference's open item "VecStats": Min(index), Max(index), Mean, Power).  min / max are
+    by |c|^2 in f64, ties to the lowest index; samples with a NaN component are counted in `n_nan` and skipped (all NaN:
+    both indices are `n`).  `raw` is the C struct, byte for byte."""
+    __slots__ = ("n", "n_nan", "min_index", "max_index", "min_norm", "max_norm", "mean", "power", "raw")
+
+    def __init__(self, c):
+        self.n, self.n_nan, self.min_index, self.max_index = c.n, c.n_nan, c.min_index, c.max_index
+        self.min_norm, self.max_norm = np.float32(c.min_norm), np.float32(c.max_norm)
+        self.mean = complex(c.mean_re, c.mean_im)
+        self.power = c.power
+        self.raw = bytes(c)
+
+    def __repr__(self):
+        return (f"VecStats(n={self.n}, n_nan={self.n_nan}, min={self.min_norm!r}@{self.min_index}, "
+                f"max={self.max_norm!r}@{self.max_index}, mean={self.mean!r}, power={self.power!r})")
+
+
 class Context:
     """One device + one HIP stream (aeth_ctx).  Not thread-safe, like `&mut self`."""
 
@@ -127,6 +156,42 @@ class Event:
             pass
 
 
+class DeviceF32:
+    """Device-resident `[f32]`: the levels of a vector or of a batch of spectra."""
+
+    def __init__(self, ctx, n, ptr=None, offset=0, owner=None):
+        self.ctx, self.n, self._owner = ctx, int(n), owner
+        if ptr is None:
+            self._base = ctx.alloc(max(self.n, 1) * 4)
+            self.ptr, self._owns = self._base, True
+        else:
+            self._base, self.ptr, self._owns = ptr, ptr + offset * 4, False
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        try:
+            if self._owns and self._base and self.ctx.h:
+                self.ctx.free(self._base)
+                self._base = None
+        except Exception:
+            pass
+
+    def slice(self, start, stop):
+        assert 0 <= start <= stop <= self.n
+        return DeviceF32(self.ctx, stop - start, ptr=self.ptr, offset=start, owner=self)
+
+    def to_host(self):
+        out = np.empty(self.n, np.float32)
+        if self.n:
+            self.ctx.download(self.ptr, out)
+        return out
+
+    def _p(self):
+        return C.c_void_p(self.ptr)
+
+
 class DeviceVec:
     """Device-resident `[cf32]` with the VecOps method set (src/vecops.rs:39-89)."""
 
@@ -178,6 +243,21 @@ class DeviceVec:
         if isinstance(other, DeviceVec):
             return other
         return self.ctx.vec(other)      # host slice given: stage it (AsRef<[cf32]>)
+
+    # ---- numbers and levels (aeth_vec_stats / aeth_vec_levels; no body in the reference yet) ----
+    def stats(self):
+        """One read-only pass: count, NaN count, min / max by norm with their indices, mean, power -> VecStats.
+        Waits for the 64-byte record; nothing else leaves the device."""
+        c = _VecStats()
+        check(self.ctx._lib.aeth_vec_stats(self.ctx.h, self._p(), self.n, C.byref(c)))
+        return VecStats(c)
+
+    def levels(self, kind=LEVEL_NORM, out=None):
+        """norm() (LEVEL_NORM), the reference's DB::from(norm).db() (LEVEL_DB: 10 * log10 of the amplitude, its quirk)
+        or the power in dB (LEVEL_POWER_DB) of every sample (util/plot.rs:65,127) -> DeviceF32; self is not modified."""
+        out = DeviceF32(self.ctx, self.n) if out is None else out
+        check(self.ctx._lib.aeth_vec_levels(self.ctx.h, self._p(), self.n, int(kind), out._p(), out.n))
+        return out
 
     # ---- trait VecOps ----
     def vec_scale(self, scale):                                   # vecops.rs:41
@@ -290,6 +370,12 @@ class HostVec:
         o = _c64(other)
         check(getattr(self.ctx._lib, name)(self.ctx.h, self._p(), self.a.size, o.ctypes.data_as(C.c_void_p), o.size))
         return self
+
+    def stats(self):
+        """VecStats of the host slice, computed on the device (the same record, bit for bit, as DeviceVec.stats())"""
+        c = _VecStats()
+        check(self.ctx._lib.aeth_host_vec_stats(self.ctx.h, self._p(), self.a.size, C.byref(c)))
+        return VecStats(c)
 
     def vec_scale(self, s):
         check(self.ctx._lib.aeth_host_vec_scale(self.ctx.h, self._p(), self.a.size, float(np.float32(s)))); return self

@@ -25,6 +25,7 @@
 #include "aeth_internal.h"
 #include "aeth_fft_core.h"
 #include "aeth_fft_plan.h"
+#include "aeth_levels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -53,7 +54,10 @@ template <class C> struct SingleImage : C {
 };
 
 // NT: frames are streamed with the non-temporal hint (batches beyond the cache; aeth_internal.h)
-template <class C0, int S, bool NT>
+// LK: store kind.  -1: the spectrum (8 bytes per bin).  AETH_LEVEL_*: `out` is a float buffer and the level of every bin
+// (aeth_levels.h, of the scaled bin exactly as it would have been stored) goes where the bin would: 4 bytes per bin, the
+// spectrum is never written (aeth_fft_exec_levels)
+template <class C0, int S, bool NT, int LK = -1>
 __global__ __launch_bounds__(C0::WG) void fft_pow2_kernel(const cf *in, cf *out,
                                                           const cf *__restrict__ twL, size_t batch, float scale, int mirror)
 {
@@ -116,7 +120,33 @@ __global__ __launch_bounds__(C0::WG) void fft_pow2_kernel(const cf *in, cf *out,
         else fft_in_regs<C, S, 1>(w, tw, lds, tid);
         par = (fft_next_par<C>(0) != 0) && !par;
         const cf ss = mk(scale, scale);
-        if constexpr (STAGED) {
+        if constexpr (LK >= 0) {
+            float *lv_out = reinterpret_cast<float *>(out);
+            if constexpr (STAGED) {
+                float *lds_lv = reinterpret_cast<float *>(lds_io);
+                __syncthreads();
+                if (fl < C::F) {
+#pragma unroll
+                    for (int m = 0; m < C::P; m++) {
+                        const cf v = cscale_k(w[m], ss);
+                        lds_lv[fl * (C::N + 1) + tid + m * C::T + (m < C::P / 2 ? msh : -msh)] = aeth::level_of<LK>(v.x, v.y);
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < (C::F * C::N + C::WG - 1) / C::WG; q++) {
+                    const int e = threadIdx.x + q * C::WG;
+                    if (e < have) aeth::nt_store<NT>(lv_out + base + e, lds_lv[e + e / C::N]);
+                }
+            } else if (active) {
+                float *dlv = lv_out + frame * C::N + tid;
+#pragma unroll
+                for (int m = 0; m < C::P; m++) {
+                    const cf v = cscale_k(w[m], ss);
+                    aeth::nt_store<NT>(dlv + m * C::T + (m < C::P / 2 ? msh : -msh), aeth::level_of<LK>(v.x, v.y));
+                }
+            }
+        } else if constexpr (STAGED) {
             __syncthreads();
             if (fl < C::F) {
 #pragma unroll
@@ -142,7 +172,7 @@ __global__ __launch_bounds__(C0::WG) void fft_pow2_kernel(const cf *in, cf *out,
 // while this one is transformed, table loads drained once before the loop.
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-template <class C, int S, bool NT>
+template <class C, int S, bool NT, int LK = -1>
 __global__ __launch_bounds__(C::WG) void fft_pow2_stream_kernel(const cf *in, cf *out, const cf *__restrict__ twL,
                                                                  size_t batch, float scale, int mirror)
 {
@@ -174,6 +204,16 @@ __global__ __launch_bounds__(C::WG) void fft_pow2_stream_kernel(const cf *in, cf
         if (fft_next_par<C>(0) == 0 || !par) fft_in_regs<C, S, 0>(w, tw, lds, tid);
         else fft_in_regs<C, S, 1>(w, tw, lds, tid);
         par = (fft_next_par<C>(0) != 0) && !par;
+        if constexpr (LK >= 0) {                            // levels: 4 bytes per bin, half the byte offsets
+            auto ls = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float *>(out) + g * C::N, 0, C::N * 4, 0x00020000);
+#pragma unroll
+            for (int m = 0; m < C::P; m++) {
+                const cf v = cscale_k(w[m], ss);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, aeth::level_of<LK>(v.x, v.y)), ls,
+                                                      (tid + m * C::T) * 4 + (m < C::P / 2 ? msh / 2 : -(msh / 2)), 0, NT ? 18 : 0);
+            }
+            continue;
+        }
         auto ws = __builtin_amdgcn_make_buffer_rsrc(out + g * C::N, 0, C::N * 8, 0x00020000);
 #pragma unroll
         for (int m = 0; m < C::P; m++)
@@ -181,11 +221,12 @@ __global__ __launch_bounds__(C::WG) void fft_pow2_stream_kernel(const cf *in, cf
     }
 }
 
-template <class C>
+template <class C, int LK = -1>
 int launch_pow2(const aeth_fft *plan, const float2 *in, float2 *out, size_t batch, int sign, float scale, int mirror)
 {
     const aeth_ctx *ctx = plan->ctx;
-    const bool nt = aeth::streams_past_cache(2 * batch * (size_t)C::N * sizeof(float2));
+    // bytes moved: a frame in and a frame (or, LK >= 0, its levels: half the bytes) out
+    const bool nt = aeth::streams_past_cache((LK >= 0 ? 3 : 4) * batch * (size_t)C::N * (sizeof(float2) / 2));
     size_t ngroups = (batch + C::F - 1) / C::F;
     size_t cap = (size_t)ctx->num_cus * 8;
     int grid = (int)(ngroups < cap ? ngroups : cap);
@@ -196,7 +237,7 @@ int launch_pow2(const aeth_fft *plan, const float2 *in, float2 *out, size_t batc
         int grid2 = (int)(batch < cap2 ? batch : cap2);
         if (grid2 < 1) grid2 = 1;
         if (!aeth::lab_int("AETH_FFT_NOSTREAM", 0)) {
-#define AETH_FFT_STREAM(SS, NN) hipLaunchKernelGGL((fft_pow2_stream_kernel<C, SS, NN>), dim3(grid2), dim3(C::WG), 0, aeth::ctx_stream(ctx), (const cf *)in, (cf *)out, (const cf *)plan->tw_lane_dev, batch, scale, mirror)
+#define AETH_FFT_STREAM(SS, NN) hipLaunchKernelGGL((fft_pow2_stream_kernel<C, SS, NN, LK>), dim3(grid2), dim3(C::WG), 0, aeth::ctx_stream(ctx), (const cf *)in, (cf *)out, (const cf *)plan->tw_lane_dev, batch, scale, mirror)
             if (sign > 0) { if (nt) AETH_FFT_STREAM(+1, true); else AETH_FFT_STREAM(+1, false); }
             else          { if (nt) AETH_FFT_STREAM(-1, true); else AETH_FFT_STREAM(-1, false); }
 #undef AETH_FFT_STREAM
@@ -204,7 +245,7 @@ int launch_pow2(const aeth_fft *plan, const float2 *in, float2 *out, size_t batc
             return AETH_OK;
         }
     }
-#define AETH_FFT_PLAIN(SS, NN) hipLaunchKernelGGL((fft_pow2_kernel<C, SS, NN>), dim3(grid), dim3(C::WG), 0, aeth::ctx_stream(ctx), (const cf *)in, (cf *)out, (const cf *)plan->tw_lane_dev, batch, scale, mirror)
+#define AETH_FFT_PLAIN(SS, NN) hipLaunchKernelGGL((fft_pow2_kernel<C, SS, NN, LK>), dim3(grid), dim3(C::WG), 0, aeth::ctx_stream(ctx), (const cf *)in, (cf *)out, (const cf *)plan->tw_lane_dev, batch, scale, mirror)
     if (sign > 0) { if (nt) AETH_FFT_PLAIN(+1, true); else AETH_FFT_PLAIN(+1, false); }
     else          { if (nt) AETH_FFT_PLAIN(-1, true); else AETH_FFT_PLAIN(-1, false); }
 #undef AETH_FFT_PLAIN
@@ -216,6 +257,15 @@ int dispatch_pow2(const aeth_fft *plan, const float2 *in, float2 *out, size_t ba
 {
 #define AETH_BODY(NN) return launch_pow2<typename CfgFor<NN>::type>(plan, in, out, batch, sign, scale, mirror)
     AETH_POW2_SWITCH_XL(plan->len, AETH_BODY, return aeth::set_error(AETH_E_UNSUPPORTED, "stockham_pow2: length %zu", plan->len))
+#undef AETH_BODY
+}
+
+// the same transforms with the level of every bin stored instead of the bin (`lv` takes the place of `out`)
+template <int LK>
+int dispatch_pow2_levels(const aeth_fft *plan, const float2 *in, float *lv, size_t batch, int sign, float scale, int mirror)
+{
+#define AETH_BODY(NN) return launch_pow2<typename CfgFor<NN>::type, LK>(plan, in, reinterpret_cast<float2 *>(lv), batch, sign, scale, mirror)
+    AETH_POW2_SWITCH(plan->len, AETH_BODY, return aeth::set_error(AETH_E_UNSUPPORTED, "stockham_pow2 levels: length %zu", plan->len))
 #undef AETH_BODY
 }
 
@@ -934,6 +984,40 @@ int aeth_fft_exec_mirrored(aeth_fft *p, const aeth_cf32 *in, size_t n_in, aeth_c
     }
     rc = aeth::fft_run(p, (const float2 *)in, (float2 *)out, batch, sign, s); if (rc) return rc;
     return aeth_vec_mirror_frames(p->ctx, out, p->len, batch);              /* vecops.rs:157-161 per frame */
+}
+
+/* per frame: the transform with its Scale, vec_mirror if asked for, then the level of every bin: `waterfall` and `spectrum`
+ * of src/util/plot.rs:46-68, :109-130 (c.norm(), DB::from(c).db()) in one call; `in` is left as it was */
+int aeth_fft_exec_levels(aeth_fft *p, const aeth_cf32 *in, size_t n_in, size_t batch, int sign, int kind, float x,
+                         int mirror, int level_kind, float *levels, size_t n_levels)
+{
+    int rc = check_exec(p, sign, kind); if (rc) return rc;
+    AETH_REQUIRE(aeth::level_kind_ok(level_kind), AETH_E_ARG, "bad level kind %d", level_kind);
+    AETH_REQUIRE(n_in == batch * p->len, AETH_E_LEN, AETH_MSG_FFT_LEN);     /* fft.rs:163-167 */
+    AETH_REQUIRE(n_levels == n_in, AETH_E_LEN, "Levels and samples must have same length");
+    if (batch == 0 || p->len == 0) return AETH_OK;
+    AETH_REQUIRE(in && levels, AETH_E_ARG, "null pointer");
+    AETH_REQUIRE(aeth::aligned8(in), AETH_E_ALIGN, "pointer not 8-byte aligned");
+    AETH_REQUIRE((reinterpret_cast<uintptr_t>(levels) & 3u) == 0, AETH_E_ALIGN, "levels not 4-byte aligned");
+    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + n_in * sizeof(aeth_cf32), b0 = (uintptr_t)levels, b1 = b0 + n_in * sizeof(float);
+    AETH_REQUIRE(a1 <= b0 || b1 <= a0, AETH_E_ARG, "levels overlaps the input");
+    const float s = aeth_scale_factor(kind, p->len, x);
+    if (p->algo == aeth::FFT_ALGO_POW2 && p->len >= 2 && p->len <= 4096) {
+        // register-resident transforms: the level is taken of the scaled bin in registers, the spectrum is never written
+        aeth::DeviceGuard dev_guard(p->ctx->device);
+        const int m = mirror ? 1 : 0;
+        switch (level_kind) {
+        case AETH_LEVEL_NORM: return dispatch_pow2_levels<AETH_LEVEL_NORM>(p, (const float2 *)in, levels, batch, sign, s, m);
+        case AETH_LEVEL_DB:   return dispatch_pow2_levels<AETH_LEVEL_DB>(p, (const float2 *)in, levels, batch, sign, s, m);
+        default:              return dispatch_pow2_levels<AETH_LEVEL_POWER_DB>(p, (const float2 *)in, levels, batch, sign, s, m);
+        }
+    }
+    // every other algorithm: the spectrum through the plan's temp (Cfft.tmp, fft.rs:141), as aeth_fft_exec_mirrored and
+    // aeth_vec_levels would do it
+    rc = ensure_temps(p, n_in, false); if (rc) return rc;
+    rc = aeth::fft_run(p, (const float2 *)in, p->tmp_dev, batch, sign, s); if (rc) return rc;
+    if (mirror) { rc = aeth_vec_mirror_frames(p->ctx, (aeth_cf32 *)p->tmp_dev, p->len, batch); if (rc) return rc; }
+    return aeth_vec_levels(p->ctx, (const aeth_cf32 *)p->tmp_dev, n_in, level_kind, levels, n_levels);
 }
 
 /* per frame: c.vec_rfft / vec_rifft (sign, scale) then sampling::interpolate(&c, &mut dst, n_between) (sampling.rs:7-24);

@@ -44,6 +44,9 @@ struct aeth_ctx {
     void *bounce[2] = {nullptr, nullptr};
     // plans of the one-shot vec_fft / vec_ifft (aeth_fft.hip: fft_cache_get), most recently used first
     void *fft_cache = nullptr;
+    // per-workgroup partial records of aeth_vec_stats (aeth_stats.hip), grown on demand, released by aeth_ctx_trim
+    void *stats_slab = nullptr;
+    size_t stats_slab_bytes = 0;
 };
 
 namespace aeth {
@@ -63,6 +66,8 @@ hipStream_t ctx_fir_lane(aeth_ctx *ctx, uintptr_t in_lo, uintptr_t in_hi, uintpt
 int ctx_stage(aeth_ctx *ctx, int i, size_t bytes);
 // frees the plans vec_fft / vec_ifft built for this context (aeth_ctx_destroy, aeth_ctx_trim)
 void fft_cache_release(aeth_ctx *ctx);
+// frees the slab of aeth_vec_stats (aeth_ctx_destroy, aeth_ctx_trim)
+void stats_slab_release(aeth_ctx *ctx);
 
 // Buffers of one host-slice call (the literal trait call: host slice in, host slice out, synchronous).
 //   small (every buffer <= kZeroCopyMax): the context's two pinned, device-visible bounce buffers -- memcpy in, the kernel

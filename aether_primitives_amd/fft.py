@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .context import DeviceVec
+from .context import DeviceF32, DeviceVec, LEVEL_NORM
 
 # exponent sign bound to the reference's method names in exactly one place:
 # Cfft::with_len plans `fwd` with FFTplanner::new(true) (= rustfft "inverse", +j)
@@ -110,6 +110,16 @@ class HipFft:
         n = self.len()
         check(self._lib.aeth_fft_exec_mirrored(self.h, frames._p(), frames.n, out._p(), frames.n // n if n else 0,
                                                SIGN_REF_FWD, s.kind, s.x))
+        return out
+
+    def levels(self, frames, s=Scale.NONE, mirror=False, kind=LEVEL_NORM, out=None, sign=SIGN_REF_FWD):
+        """every frame: vec_rfft(self, s), vec_mirror() if `mirror`, then the level of every bin (util/plot.rs:46-68 and
+        :109-130: `waterfall` and `spectrum`) in one call -> DeviceF32 of frames.n levels; `frames` stays as it was.
+        Power-of-two lengths up to 4096 never write the spectrum."""
+        n = self.len()
+        out = DeviceF32(self.ctx, frames.n) if out is None else out
+        check(self._lib.aeth_fft_exec_levels(self.h, frames._p(), frames.n, frames.n // n if n else 0, sign, s.kind, s.x,
+                                             1 if mirror else 0, int(kind), out._p(), out.n))
         return out
 
     def rfft_interpolate(self, frames, dst, n_between, s=Scale.NONE, compat_im=True):

@@ -169,6 +169,44 @@ AETH_API int aeth_host_vec_mirror(aeth_ctx *ctx, aeth_cf32 *self_, size_t n);
 AETH_API int aeth_host_vec_clone (aeth_ctx *ctx, aeth_cf32 *self_, size_t n, const aeth_cf32 *other, size_t n_other);
 AETH_API int aeth_host_vec_zero  (aeth_ctx *ctx, aeth_cf32 *self_, size_t n);
 
+/* ---- VecStats and levels (no body in the reference yet) -------------------- */
+/* The reference lists "Add VecStats (f32, cf32): Min(index), Max(index), Mean(index), Power" as an open item
+ * (README.md:90-91) and maps every bin of a spectrum through c.norm() and, with use_db, DB::from(c).db()
+ * (src/util/plot.rs:65,127; src/util/mod.rs:26-34: 10 * log10(ratio) in f64).  Both are defined here so that they can
+ * be reproduced exactly with IEEE operations (csrc/aeth_levels.h), for a sample c = (re, im):
+ *   q(c)    = (double)re * re + (double)im * im      one rounding of |c|^2, the same bits with or without fma
+ *   norm(c) = (float)sqrt(q(c))                      Complex::norm() = hypot without hypot's platform dependence
+ * Level kinds:
+ *   AETH_LEVEL_NORM      norm(c)
+ *   AETH_LEVEL_DB        (float)(10.0 * log10((double)norm(c))), the reference's literal DB::from(c.norm()).db().  This is
+ *                        10 * log10 of an AMPLITUDE: the reference's quirk (a power level would be 20 * log10), kept as
+ *                        the default like its other quirks
+ *   AETH_LEVEL_POWER_DB  (float)(10.0 * log10(q(c))), the corrected form
+ * norm = 0 gives -inf and a NaN component gives NaN, as Rust's f64::log10 does. */
+enum { AETH_LEVEL_NORM = 0, AETH_LEVEL_DB = 1, AETH_LEVEL_POWER_DB = 2 };
+/* One read-only pass over x (8 B per sample).  min / max are ordered by q (f64), ties go to the LOWEST index (numpy's
+ * argmin / argmax); samples with a NaN component are counted in n_nan and are not candidates (all NaN: both indices
+ * are n, both norms NaN).  The sums include NaN samples, so mean and power are NaN then, as IEEE says, and n_nan tells
+ * why.  "Mean(index)" of the reference's list has no meaning that could be pinned down and is left out.
+ * Bitwise reproducible: the f64 sums are combined in an order that depends on the element index and n only -- not on
+ * the device's CU count, the pointer's alignment, the cache policy (AETH_NT) or host / device flavour.  Element counts
+ * and indices are size_t throughout.  The struct shares its name with the function, so C and C++ callers alike
+ * spell the type `struct aeth_vec_stats`. */
+struct aeth_vec_stats {
+    size_t n, n_nan;              /* samples; samples with a NaN component                       */
+    size_t min_index, max_index;  /* LOWEST index among equal q; NaN samples are not candidates  */
+    float  min_norm, max_norm;    /* norm() of those two samples                                 */
+    double mean_re, mean_im;      /* sum(re) / n, sum(im) / n, accumulated in f64                */
+    double power;                 /* sum(q) / n, accumulated in f64                              */
+};
+/* n == 0 -> AETH_E_LEN.  Waits for the result (the record is 64 bytes). */
+AETH_API int aeth_vec_stats(aeth_ctx *ctx, const aeth_cf32 *x_dev, size_t n, struct aeth_vec_stats *out_host);
+AETH_API int aeth_host_vec_stats(aeth_ctx *ctx, const aeth_cf32 *x_host, size_t n, struct aeth_vec_stats *out_host);
+/* levels_dev[i] = level of x_dev[i] (8 B in, 4 B out per sample).  Stream-ordered, x_dev is not modified, the two
+ * ranges must not overlap (AETH_E_ARG), levels_dev 4-byte aligned; n_levels != n -> AETH_E_LEN. */
+AETH_API int aeth_vec_levels(aeth_ctx *ctx, const aeth_cf32 *x_dev, size_t n, int level_kind,
+                             float *levels_dev, size_t n_levels);
+
 /* ---- Scale: src/fft.rs:22-37 ---------------------------------------------- */
 /* factor exactly as the reference computes it in f32: SN -> (n as f32).sqrt().recip(),
  * N -> (n as f32).recip(), X -> x, None -> 1 (and no pass at all). */
@@ -193,6 +231,15 @@ AETH_API int aeth_fft_exec(aeth_fft *plan, const aeth_cf32 *in, size_t n_in, aet
  * is folded into the transform's store addresses (no second pass over memory), other lengths run the two steps. */
 AETH_API int aeth_fft_exec_mirrored(aeth_fft *plan, const aeth_cf32 *in_dev, size_t n_in, aeth_cf32 *out_dev,
                                     size_t batch, int sign, int scale_kind, float x);
+/* The whole `waterfall` / `spectrum` computation (src/util/plot.rs:46-68, :109-130) in one call, per frame: the
+ * transform with its Scale, vec_mirror if mirror != 0, then the level of every bin (level kinds: see aeth_vec_levels).
+ * in_dev is not modified.  Bit-identical to aeth_fft_exec / aeth_fft_exec_mirrored into a scratch buffer followed by
+ * aeth_vec_levels.  For the register-resident power-of-two lengths the level is taken in registers and a 4-byte value
+ * is stored where the 8-byte bin would go: the spectrum is never written (12 B per sample).  Other lengths run the
+ * transform into the plan's temp (Cfft.tmp), then the levels kernel. */
+AETH_API int aeth_fft_exec_levels(aeth_fft *plan, const aeth_cf32 *in_dev, size_t n_in, size_t batch, int sign,
+                                  int scale_kind, float x, int mirror, int level_kind,
+                                  float *levels_dev, size_t n_levels);
 /* Per frame: the transform, then sampling::interpolate(&frame, &mut dst, n_between) (src/sampling.rs:7-24) -- BASELINE
  * config 5's chain in one call.  dst receives batch frames of len + (len-1)*n_between samples; `in` is not modified.
  * The spectrum goes through the plan's temp (Cfft.tmp); bit-identical to aeth_fft_exec + aeth_interpolate_frames. */

@@ -70,6 +70,38 @@ private:
 
 class HipFft;
 
+// level kinds of DeviceVec::levels / HipFft::levels (AETH_LEVEL_*): norm(), the reference's DB::from(norm).db()
+// (10 * log10 of the amplitude: its quirk), the power in dB
+enum class Level : int { Norm = AETH_LEVEL_NORM, Db = AETH_LEVEL_DB, PowerDb = AETH_LEVEL_POWER_DB };
+using VecStats = struct ::aeth_vec_stats;     // the record of aeth_vec_stats, field for field
+
+// device-resident [f32]: the levels of a vector or of a batch of spectra
+class DeviceF32 {
+public:
+    DeviceF32(Context &ctx, size_t n) : ctx_(&ctx), n_(n)
+    {
+        void *p = nullptr;
+        check(aeth_dev_alloc(ctx.get(), (n ? n : 1) * sizeof(float), &p));
+        p_ = static_cast<float *>(p);
+    }
+    ~DeviceF32() { if (p_) aeth_dev_free(ctx_->get(), p_); }
+    DeviceF32(const DeviceF32 &) = delete;
+    DeviceF32 &operator=(const DeviceF32 &) = delete;
+    DeviceF32(DeviceF32 &&o) noexcept : ctx_(o.ctx_), p_(o.p_), n_(o.n_) { o.p_ = nullptr; }
+    size_t len() const { return n_; }
+    float *ptr() const { return p_; }
+    std::vector<float> to_host() const
+    {
+        std::vector<float> h(n_);
+        check(aeth_download(ctx_->get(), h.data(), p_, n_ * sizeof(float)));
+        return h;
+    }
+private:
+    Context *ctx_;
+    float *p_ = nullptr;
+    size_t n_ = 0;
+};
+
 // ---- trait VecOps, device-resident receiver (src/vecops.rs:39-89) ------------------
 class DeviceVec {
 public:
@@ -121,6 +153,15 @@ public:
         for (auto &z : h) f(z);
         check(aeth_upload(c(), p_, h.data(), n_ * sizeof(cf32)));
         return *this;
+    }
+    // the reference's open item "VecStats" (README.md:90-91): one read-only pass, waits for the 64-byte record
+    VecStats stats() const { VecStats st{}; check(aeth_vec_stats(c(), p_, n_, &st)); return st; }
+    // the level of every sample (util/plot.rs:65,127); *this is not modified
+    DeviceF32 levels(Level kind = Level::Norm) const
+    {
+        DeviceF32 out(*ctx_, n_);
+        check(aeth_vec_levels(c(), p_, n_, static_cast<int>(kind), out.ptr(), out.len()));
+        return out;
     }
     inline DeviceVec &vec_fft(Scale s);                    // fresh plan (src/vecops.rs:185-189)
     inline DeviceVec &vec_ifft(Scale s);
@@ -199,6 +240,16 @@ public:
         check(aeth_fft_mul_ifft(h_, frames.ptr(), frames.len(), n ? frames.len() / n : 0, sig.ptr(), sig.len(),
                                 s_fwd.kind, s_fwd.x, s_bwd.kind, s_bwd.x));
     }
+    // per frame: vec_rfft(s), vec_mirror() if asked for, then the level of every bin -- `waterfall` / `spectrum` of
+    // util/plot.rs:46-68, :109-130 in one call; `frames` stays as it was
+    DeviceF32 levels(const DeviceVec &frames, Scale s, bool mirror = false, Level kind = Level::Norm)
+    {
+        size_t n = len();
+        DeviceF32 out(frames.ctx(), frames.len());
+        check(aeth_fft_exec_levels(h_, frames.ptr(), frames.len(), n ? frames.len() / n : 0, kFwdSign, s.kind, s.x,
+                                   mirror ? 1 : 0, static_cast<int>(kind), out.ptr(), out.len()));
+        return out;
+    }
     aeth_fft *get() const { return h_; }
 
 private:
@@ -228,6 +279,7 @@ class HostVec {
 public:
     HostVec(Context &ctx, cf32 *data, size_t n) : ctx_(&ctx), p_(data), n_(n) {}
     HostVec(Context &ctx, std::vector<cf32> &v) : HostVec(ctx, v.data(), v.size()) {}
+    VecStats stats() const { VecStats st{}; check(aeth_host_vec_stats(c(), raw(p_), n_, &st)); return st; }
     HostVec &vec_scale(float s) { check(aeth_host_vec_scale(c(), raw(p_), n_, s)); return *this; }
     HostVec &vec_mul(const std::vector<cf32> &o) { check(aeth_host_vec_mul(c(), raw(p_), n_, raw(o.data()), o.size())); return *this; }
     HostVec &vec_div(const std::vector<cf32> &o) { check(aeth_host_vec_div(c(), raw(p_), n_, raw(o.data()), o.size())); return *this; }

@@ -18,6 +18,12 @@ pub struct aeth_pipe_stats { pub seconds: f64, pub samples: f64, pub chunks: f64
 pub struct aeth_vec_step { pub op: c_int, pub other_dev: *const cf32, pub n_other: usize, pub scale: c_float }
 pub const AETH_VEC_SCALE: c_int = 0; pub const AETH_VEC_MUL: c_int = 1; pub const AETH_VEC_DIV: c_int = 2; pub const AETH_VEC_CONJ: c_int = 3;
 pub const AETH_VEC_ADD: c_int = 4; pub const AETH_VEC_SUB: c_int = 5; pub const AETH_VEC_CLONE: c_int = 6; pub const AETH_VEC_ZERO: c_int = 7;
+/// aeth_vec_stats (the struct): what aeth_vec_stats / aeth_host_vec_stats (the functions) fill in
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aeth_vec_stats_t { pub n: usize, pub n_nan: usize, pub min_index: usize, pub max_index: usize, pub min_norm: c_float,
+                              pub max_norm: c_float, pub mean_re: f64, pub mean_im: f64, pub power: f64 }
+pub const AETH_LEVEL_NORM: c_int = 0; pub const AETH_LEVEL_DB: c_int = 1; pub const AETH_LEVEL_POWER_DB: c_int = 2;
 /// aeth_stream_op: the compute stage of the host pipeline (src/pipeline.rs:24-41 takes a closure; a closure cannot
 /// cross the C ABI, so the stage is one of the library's device ops, described field by field as in aether_hip.h)
 #[repr(C)]
@@ -88,6 +94,9 @@ extern "C" {
     pub fn aeth_vec_clone(ctx: *mut aeth_ctx, s: *mut cf32, n: usize, o: *const cf32, no: usize) -> c_int;
     pub fn aeth_vec_zero(ctx: *mut aeth_ctx, s: *mut cf32, n: usize) -> c_int;
     pub fn aeth_vec_mirror_frames(ctx: *mut aeth_ctx, s: *mut cf32, frame_len: usize, batch: usize) -> c_int;
+    pub fn aeth_vec_stats(ctx: *mut aeth_ctx, x: *const cf32, n: usize, out: *mut aeth_vec_stats_t) -> c_int;
+    pub fn aeth_host_vec_stats(ctx: *mut aeth_ctx, x: *const cf32, n: usize, out: *mut aeth_vec_stats_t) -> c_int;
+    pub fn aeth_vec_levels(ctx: *mut aeth_ctx, x: *const cf32, n: usize, level_kind: c_int, levels: *mut c_float, n_levels: usize) -> c_int;
     // host-slice flavours: the literal `impl VecOps for [cf32]` semantics, one H2D + D2H per call
     pub fn aeth_host_vec_scale(ctx: *mut aeth_ctx, s: *mut cf32, n: usize, scale: c_float) -> c_int;
     pub fn aeth_host_vec_mul(ctx: *mut aeth_ctx, s: *mut cf32, n: usize, o: *const cf32, no: usize) -> c_int;
@@ -110,6 +119,8 @@ extern "C" {
     pub fn aeth_fft_exec(plan: *mut aeth_fft, inp: *const cf32, n_in: usize, out: *mut cf32, batch: usize,
                          sign: c_int, scale_kind: c_int, x: c_float) -> c_int;
     pub fn aeth_fft_exec_mirrored(plan: *mut aeth_fft, inp: *const cf32, n_in: usize, out: *mut cf32, batch: usize, sign: c_int, kind: c_int, x: c_float) -> c_int;
+    pub fn aeth_fft_exec_levels(plan: *mut aeth_fft, inp: *const cf32, n_in: usize, batch: usize, sign: c_int, kind: c_int, x: c_float,
+                                mirror: c_int, level_kind: c_int, levels: *mut c_float, n_levels: usize) -> c_int;
     pub fn aeth_fft_exec_interpolate(plan: *mut aeth_fft, inp: *const cf32, n_in: usize, batch: usize, sign: c_int, kind: c_int, x: c_float,
                                      dst: *mut cf32, dst_cap: usize, n_between: usize, compat_im: c_int, n_written: *mut usize) -> c_int;
     pub fn aeth_fft_exec_host(plan: *mut aeth_fft, inp: *const cf32, n_in: usize, out: *mut cf32, n_out: usize,

@@ -63,6 +63,15 @@ impl<'c> HipFft<'c> {
         let (k, x) = scale_args(s);
         check(unsafe { aeth_fft_exec_host(self.h, input, n_in, output, n_out, sign, k, x) });
     }
+    /// per frame: `vec_rfft(self, s)`, `vec_mirror()` if asked for, then the level of every bin: `waterfall` / `spectrum`
+    /// of src/util/plot.rs:46-68, :109-130 in one call; `frames` stays as it was
+    pub fn levels<'v>(&mut self, frames: &DeviceVec<'v>, s: Scale, mirror: bool, kind: Level) -> DeviceF32<'v> {
+        let (k, x) = scale_args(s);
+        let batch = if self.len() > 0 { frames.n / self.len() } else { 0 };
+        let out = DeviceF32::new(frames.ctx, frames.n);
+        check(unsafe { aeth_fft_exec_levels(self.h, frames.p, frames.n, batch, AETH_SIGN_REF_FWD, k, x, mirror as i32, kind as i32, out.p, out.n) });
+        out
+    }
     fn tmp(&mut self, input: &[cf32], sign: i32, s: Scale) -> &[cf32] {
         let (k, x) = scale_args(s);
         let mut view: *const cf32 = ptr::null();
@@ -93,6 +102,30 @@ impl<'c> Fft for HipFft<'c> {
     fn len(&self) -> usize { unsafe { aeth_fft_len(self.h) } }
 }
 
+/// level kinds (AETH_LEVEL_*): `norm()`, the reference's `DB::from(norm).db()` (10 * log10 of the amplitude: its
+/// quirk), the power in dB
+#[derive(Clone, Copy)]
+pub enum Level { Norm = 0, Db = 1, PowerDb = 2 }
+/// the reference's open item "VecStats" (README.md:90-91)
+pub type VecStats = aeth_vec_stats_t;
+
+/// Device-resident `[f32]`: the levels of a vector or of a batch of spectra.
+pub struct DeviceF32<'c> { ctx: &'c Context, p: *mut f32, n: usize }
+impl<'c> DeviceF32<'c> {
+    pub fn new(ctx: &'c Context, n: usize) -> DeviceF32<'c> {
+        let mut p: *mut c_void = ptr::null_mut();
+        check(unsafe { aeth_dev_alloc(ctx.h, n.max(1) * 4, &mut p) });
+        DeviceF32 { ctx, p: p as *mut f32, n }
+    }
+    pub fn len(&self) -> usize { self.n }
+    pub fn to_vec(&self) -> Vec<f32> {
+        let mut v = vec![0f32; self.n];
+        check(unsafe { aeth_download(self.ctx.h, v.as_mut_ptr() as *mut c_void, self.p as *const c_void, self.n * 4) });
+        v
+    }
+}
+impl<'c> Drop for DeviceF32<'c> { fn drop(&mut self) { unsafe { aeth_dev_free(self.ctx.h, self.p as *mut c_void); } } }
+
 /// Device-resident `[cf32]` with the `VecOps` method set (src/vecops.rs:39-89).
 pub struct DeviceVec<'c> { ctx: &'c Context, p: *mut cf32, n: usize }
 impl<'c> DeviceVec<'c> {
@@ -108,6 +141,18 @@ impl<'c> DeviceVec<'c> {
         v
     }
     pub fn len(&self) -> usize { self.n }
+    /// one read-only pass: min / max by norm with their (lowest) indices, mean, power; waits for the 64-byte record
+    pub fn stats(&self) -> VecStats {
+        let mut st = VecStats::default();
+        check(unsafe { aeth_vec_stats(self.ctx.h, self.p, self.n, &mut st) });
+        st
+    }
+    /// the level of every sample (src/util/plot.rs:65,127); `self` is not modified
+    pub fn levels(&self, kind: Level) -> DeviceF32<'c> {
+        let out = DeviceF32::new(self.ctx, self.n);
+        check(unsafe { aeth_vec_levels(self.ctx.h, self.p, self.n, kind as i32, out.p, out.n) });
+        out
+    }
     pub fn vec_scale(&mut self, s: f32) -> &mut Self { check(unsafe { aeth_vec_scale(self.ctx.h, self.p, self.n, s) }); self }
     pub fn vec_mul(&mut self, o: &DeviceVec) -> &mut Self { check(unsafe { aeth_vec_mul(self.ctx.h, self.p, self.n, o.p, o.n) }); self }
     pub fn vec_div(&mut self, o: &DeviceVec) -> &mut Self { check(unsafe { aeth_vec_div(self.ctx.h, self.p, self.n, o.p, o.n) }); self }
