@@ -16,6 +16,7 @@ from .context import (Context, DeviceVec, DeviceF32, HostVec, VecStats,  # noqa:
                       LEVEL_NORM, LEVEL_DB, LEVEL_POWER_DB)
 from .fft import Scale, HipFft, SIGN_REF_FWD, SIGN_REF_BWD  # noqa: E402
 from .fir import Fir                                      # noqa: E402
+from .corr import Corr, CorrPeak                          # noqa: E402
 from . import sampling                                    # noqa: E402
 from . import modulation                                  # noqa: E402
 from . import noise                                       # noqa: E402
@@ -26,4 +27,4 @@ from .evm import assert_evm, evm_db                       # noqa: E402
 
 __all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "DeviceF32", "HostVec", "VecStats", "LEVEL_NORM",
            "LEVEL_DB", "LEVEL_POWER_DB", "Scale", "HipFft",
-           "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "sampling", "modulation", "noise", "assert_evm", "evm_db"]
+           "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "Corr", "CorrPeak", "sampling", "modulation", "noise", "assert_evm", "evm_db"]

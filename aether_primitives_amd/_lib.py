@@ -134,6 +134,14 @@ PROTOTYPES = {
     "aeth_host_vec_stats": (i32, [vp, vp, sz, vp]),
     "aeth_vec_levels": (i32, [vp, vp, sz, i32, vp, sz]),
     "aeth_fft_exec_levels": (i32, [vp, vp, sz, sz, i32, i32, f32, i32, i32, vp, sz]),
+    "aeth_corr_create": (i32, [vp, vp, sz, sz, pvp]),
+    "aeth_corr_destroy": (i32, [vp]),
+    "aeth_corr_nref": (sz, [vp]),
+    "aeth_corr_fft_len": (sz, [vp]),
+    "aeth_corr_hop": (sz, [vp]),
+    "aeth_corr_exec": (i32, [vp, vp, vp, sz, vp]),
+    "aeth_corr_exec_levels": (i32, [vp, vp, vp, sz, i32, vp, sz]),
+    "aeth_corr_search": (i32, [vp, vp, vp, sz, vp, sz, vp]),
 }
 
 _lib = None

@@ -38,6 +38,11 @@ struct aeth_fir {
     float2 *Hf = nullptr;         // fwd(taps || 0) / N  (1/N folded in: exact, N is a power of two)
 };
 
+// the correlator IS a filter: taps = the conj-reversed template (aeth_fir.hip)
+struct aeth_corr {
+    aeth_fir *fir = nullptr;
+};
+
 namespace aeth {
 
 enum { FFT_ALGO_POW2 = 1, FFT_ALGO_MIXED = 2, FFT_ALGO_FOURSTEP = 3, FFT_ALGO_BLUESTEIN = 4, FFT_ALGO_RAGGED = 5, FFT_ALGO_FOURSTEP_MIXED = 6 };

@@ -25,6 +25,7 @@
 #include "aeth_host.h"
 
 #include <cstdlib>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -113,6 +114,32 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
             return AETH_OK;
         }
     }
+    if constexpr (!(kStoreVariants && !SCALED)) {
+        if (b.levels || b.parts)
+            return aeth::set_error(AETH_E_UNSUPPORTED, "fused FFT*H*IFFT: no level-storing / peak-finding build of length %d", C::N);
+    }
+    if constexpr (kStoreVariants && !SCALED) {
+        if (b.levels || b.parts) {                          // correlator products (aeth_corr_exec_levels, aeth_corr_search)
+            // what the launch moves: the stream once, and 4 bytes per sample or 16 per wave and block
+            const bool cnt = aeth::streams_past_cache((size_t)a.n * (b.levels ? 12 : 8));
+            // the transform of the plain build, swizzle included: the epilogues' own registers (f64 q, the logarithm of
+            // the dB kinds) still fit -- N = 2048: 250 VGPRs for the peak and the norm, 255 for the dB kinds -- and
+            // MINW = 2 holds every build to 256 (tests/test_corr_resources.py checks that none of them spills for it)
+            constexpr int CV = VAR;
+#define AETH_CORR(EXTRA)                                                                                                            \
+            do {                                                                                                                    \
+                if (cnt) hipLaunchKernelGGL((fmi_kernel<C, false, 2, true, false, CV | (EXTRA)>), dim3(grid), dim3(C::WG), 0, stream, b); \
+                else hipLaunchKernelGGL((fmi_kernel<C, false, 2, false, false, CV | (EXTRA)>), dim3(grid), dim3(C::WG), 0, stream, b);    \
+            } while (0)
+            if (b.parts) AETH_CORR(V_PEAK);
+            else if (b.level_kind == AETH_LEVEL_NORM) AETH_CORR(V_LEVEL);
+            else if (b.level_kind == AETH_LEVEL_DB) AETH_CORR(V_LEVEL | V_LV_DB);
+            else AETH_CORR(V_LEVEL | V_LV_POWER_DB);
+#undef AETH_CORR
+            AETH_HIP(hipGetLastError());
+            return AETH_OK;
+        }
+    }
     // A launch that runs on its own (one queue, or the head of a chain) issues the next window's loads in four
     // instalments between the passes of the forward transform instead of one burst (V_SPREAD): 54.25 -> 53.34 us per
     // 16 Mi-sample launch on one queue, bit-identical output; beside another launch the burst form wins (47.5 against
@@ -165,9 +192,133 @@ bool touch(const aeth_cf32 *a, size_t na, const aeth_cf32 *b, size_t nb)
     return a0 < b1 && b0 < a1;
 }
 
+// ---- aeth_corr_search: from the waves' records to the per-block records and the best of the stream -------------------
+// one candidate with a GLOBAL output index; also the record a workgroup of corr_fold_kernel leaves (24 bytes)
+struct PeakBest {
+    double q;                         // -1: no candidate (q >= 0 for every candidate)
+    unsigned long long idx, nnan;
+};
+constexpr unsigned long long kNoIdx = ~0ull;
+constexpr int kFoldBlock = 256;
+
+// a (+) b in place -- larger q, or equal q and lower index: associative and commutative, so no order of combination
+// changes the result
+__device__ __forceinline__ void best_take(double &q, unsigned long long &idx, unsigned long long &nnan, double oq,
+                                          unsigned long long oidx, unsigned long long onnan)
+{
+    const bool take = oq > q || (oq == q && oidx < idx);
+    q = take ? oq : q; idx = take ? oidx : idx; nnan += onnan;
+}
+
+// the workgroup's 256 candidates -> one, valid in thread 0
+__device__ __forceinline__ void best_block_reduce(double &q, unsigned long long &idx, unsigned long long &nnan, double *lq,
+                                                  unsigned long long *li, unsigned long long *ln)
+{
+#pragma unroll
+    for (int mask = 32; mask >= 1; mask >>= 1) {
+        const double oq = __shfl_xor(q, mask);
+        const unsigned long long oi = __shfl_xor(idx, mask), on = __shfl_xor(nnan, mask);
+        best_take(q, idx, nnan, oq, oi, on);
+    }
+    const unsigned wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) { lq[wv] = q; li[wv] = idx; ln[wv] = nnan; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < kFoldBlock / 64; w++) best_take(q, idx, nnan, lq[w], li[w], ln[w]);
+    }
+}
+
+// the public record: no candidate -> index n, norm NaN; n_nan saturates at UINT32_MAX
+__device__ __forceinline__ void peak_record(aeth_corr_peak *out, double q, unsigned long long idx, unsigned long long nnan, size_t n)
+{
+    out->index = idx == kNoIdx ? n : (size_t)idx;
+    out->norm = idx == kNoIdx ? __builtin_nanf("") : aeth::level_norm_of_q(q);
+    out->n_nan = nnan > 0xffffffffull ? 0xffffffffu : (unsigned)nnan;
+}
+
+// thread = one overlap-save block: its waves' records -> its public record (when asked for), then the workgroup's best
+__global__ __launch_bounds__(kFoldBlock) void corr_fold_kernel(const PeakPart *__restrict__ parts, long long nblocks, int waves,
+                                                               int hop, int ov, size_t n, aeth_corr_peak *__restrict__ peaks,
+                                                               PeakBest *__restrict__ wg_out)
+{
+    __shared__ double lq[kFoldBlock / 64];
+    __shared__ unsigned long long li[kFoldBlock / 64], ln[kFoldBlock / 64];
+    const long long b = (long long)blockIdx.x * kFoldBlock + threadIdx.x;
+    double q = -1.0;
+    unsigned long long idx = kNoIdx, nnan = 0;
+    if (b < nblocks) {
+        for (int w = 0; w < waves; w++) {
+            const PeakPart *p = parts + b * waves + w;
+            const unsigned e = p->e;
+            best_take(q, idx, nnan, p->q, e == kPeakNone ? kNoIdx : (unsigned long long)(b * hop - ov + (long long)e), p->nnan);
+        }
+        if (peaks) peak_record(peaks + b, q, idx, nnan, n);
+    }
+    best_block_reduce(q, idx, nnan, lq, li, ln);
+    if (threadIdx.x == 0) { wg_out[blockIdx.x].q = q; wg_out[blockIdx.x].idx = idx; wg_out[blockIdx.x].nnan = nnan; }
+}
+
+// ONE workgroup: the workgroups' records -> the record of the whole stream
+__global__ __launch_bounds__(kFoldBlock) void corr_best_kernel(const PeakBest *__restrict__ in, size_t nrec, size_t n,
+                                                               aeth_corr_peak *__restrict__ out)
+{
+    __shared__ double lq[kFoldBlock / 64];
+    __shared__ unsigned long long li[kFoldBlock / 64], ln[kFoldBlock / 64];
+    double q = -1.0;
+    unsigned long long idx = kNoIdx, nnan = 0;
+    for (size_t r = threadIdx.x; r < nrec; r += kFoldBlock) best_take(q, idx, nnan, in[r].q, in[r].idx, in[r].nnan);
+    best_block_reduce(q, idx, nnan, lq, li, ln);
+    if (threadIdx.x == 0) peak_record(out, q, idx, nnan, n);
+}
+
+int corr_slab_ensure(aeth_ctx *ctx, size_t bytes)
+{
+    if (ctx->corr_slab_bytes >= bytes) return AETH_OK;
+    if (ctx->corr_slab) {
+        AETH_HIP(hipStreamSynchronize(aeth::ctx_stream(ctx)));
+        AETH_HIP(hipFree(ctx->corr_slab));
+        ctx->corr_slab = nullptr; ctx->corr_slab_bytes = 0;
+    }
+    const size_t want = bytes + bytes / 4;
+    AETH_HIP(hipMalloc(&ctx->corr_slab, want));
+    ctx->corr_slab_bytes = want;
+    return AETH_OK;
+}
+
+// [a, a + na) and [b, b + nb) share a byte?
+bool touch_bytes(const void *a, size_t na, const void *b, size_t nb)
+{
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
+}
+
+const char kMsgFirInPlace[] = "FIR cannot run in place: the output range overlaps the input (or its history)";
+const char kMsgFirAlign[] = "pointer not 8-byte aligned";
+
+// the arguments every correlator product hands to the fused kernel (those of aeth_fir_exec)
+FmiArgs corr_args(const aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n)
+{
+    FmiArgs a;
+    a.in = (const cf *)in; a.out = nullptr; a.hist = (const cf *)hist; a.Hf = (const cf *)f->Hf;
+    a.twN = (const cf *)f->fft->tw_dev; a.twL = (const cf *)f->fft->tw_lane_dev;
+    a.n = (long long)n; a.hop = (int)f->hop; a.ov = (int)(f->fft_len - f->hop); a.nhist = (int)(f->ntaps - 1);
+    a.nblocks = (long long)((n + f->hop - 1) / f->hop);
+    a.s_fwd = 1.0f; a.s_bwd = 1.0f;
+    return a;
+}
+
 }  // namespace
 
 namespace aeth {
+
+void corr_slab_release(aeth_ctx *ctx)
+{
+    if (ctx->corr_slab) (void)hipFree(ctx->corr_slab);
+    ctx->corr_slab = nullptr;
+    ctx->corr_slab_bytes = 0;
+}
 
 // Chirp-z transform of `batch` frames of n samples in ONE launch: x*chirp -> fwd_M -> *filt -> bwd_M -> *chirp,
 // zero-padded to M = sub->len in registers (aeth_fft_big.hip: fft_run_bluestein, M <= 4096).
@@ -325,10 +476,8 @@ int aeth_fir_exec(aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, size_
     AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
     // blocks run concurrently and their windows reach into the neighbours' outputs: ANY overlap of the output range
     // with the input or the history reads samples that were already overwritten (out = in + 100 as much as out = in)
-    AETH_REQUIRE(!touch(out, n, in, n) && !touch(out, n, hist, f->ntaps - 1), AETH_E_ARG,
-                 "FIR cannot run in place: the output range overlaps the input (or its history)");
-    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(out) && aeth::aligned8(hist), AETH_E_ALIGN,
-                 "pointer not 8-byte aligned");
+    AETH_REQUIRE(!touch(out, n, in, n) && !touch(out, n, hist, f->ntaps - 1), AETH_E_ARG, "%s", kMsgFirInPlace);
+    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(out) && aeth::aligned8(hist), AETH_E_ALIGN, "%s", kMsgFirAlign);
     FmiArgs a;
     a.in = (const cf *)in; a.out = (cf *)out; a.hist = (const cf *)hist; a.Hf = (const cf *)f->Hf; a.twN = (const cf *)f->fft->tw_dev; a.twL = (const cf *)f->fft->tw_lane_dev;
     a.n = (long long)n; a.hop = (int)f->hop; a.ov = (int)(f->fft_len - f->hop); a.nhist = (int)(f->ntaps - 1);
@@ -407,6 +556,122 @@ int aeth_fir_exec_host(aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, 
     if (rc) return rc;
     AETH_HIP(hipMemcpyAsync(out, ctx->stage[1], bytes, hipMemcpyDeviceToHost, aeth::ctx_stream(ctx)));
     AETH_HIP(hipStreamSynchronize(aeth::ctx_stream(ctx)));
+    return AETH_OK;
+}
+
+}  // extern "C"
+
+/* ---- correlator: "Add Correlation by Freq. Domain Convolution" (README.md:95; the chain of benches/benches.rs:394-416
+ * run as overlap-save over a stream).  c[j] = sum_{k<M} conj(s[M-1-k]) * x[j-k] is aeth_fir_exec with the conj-reversed
+ * template as taps, so the object is a filter and nothing else; the two fused products take the level / the peak of
+ * every block in the kernel's registers (aeth_fir_kernel.h: level_block, peak_block). */
+extern "C" {
+
+int aeth_corr_create(aeth_ctx *ctx, const aeth_cf32 *ref, size_t nref, size_t fft_len, aeth_corr **out)
+{
+    AETH_REQUIRE(ctx && out, AETH_E_ARG, "null argument");
+    *out = nullptr;
+    AETH_REQUIRE(ref && nref >= 1, AETH_E_ARG, "need at least one template sample");
+    AETH_REQUIRE(is_pow2(fft_len) && fft_len >= 2 && fft_len <= 4096, AETH_E_UNSUPPORTED,
+                 "fft_len %zu: need a power of two in [2, 4096]", fft_len);
+    AETH_REQUIRE(2 * nref <= fft_len, AETH_E_ARG, "fft_len %zu < 2*nref (%zu)", fft_len, 2 * nref);
+    // the checks above are aeth_fir_create's, in the words of a template; nref <= 2048 from here on
+    std::unique_ptr<aeth_cf32[]> taps(new (std::nothrow) aeth_cf32[nref]);
+    aeth_corr *c = new (std::nothrow) aeth_corr();
+    if (!taps || !c) delete c;
+    AETH_REQUIRE(taps && c, AETH_E_NOMEM, "out of host memory");
+    for (size_t k = 0; k < nref; k++) taps[k] = aeth_cf32{ref[nref - 1 - k].re, -ref[nref - 1 - k].im};
+    const int rc = aeth_fir_create(ctx, taps.get(), nref, fft_len, &c->fir);
+    if (rc != AETH_OK) { delete c; return rc; }
+    *out = c;
+    return AETH_OK;
+}
+
+int aeth_corr_destroy(aeth_corr *c)
+{
+    if (!c) return AETH_OK;
+    const int rc = aeth_fir_destroy(c->fir);
+    delete c;
+    return rc;
+}
+
+size_t aeth_corr_nref(const aeth_corr *c) { return c ? aeth_fir_ntaps(c->fir) : 0; }
+size_t aeth_corr_fft_len(const aeth_corr *c) { return c ? aeth_fir_fft_len(c->fir) : 0; }
+size_t aeth_corr_hop(const aeth_corr *c) { return c ? aeth_fir_hop(c->fir) : 0; }
+
+int aeth_corr_exec(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, aeth_cf32 *out)
+{
+    AETH_REQUIRE(c && c->fir, AETH_E_ARG, "corr is null");
+    if (n == 0) return AETH_OK;
+    const aeth_fir *f = c->fir;
+    AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
+    AETH_REQUIRE(!touch(out, n, in, n) && !touch(out, n, hist, f->ntaps - 1), AETH_E_ARG, "%s", kMsgFirInPlace);
+    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(out) && aeth::aligned8(hist), AETH_E_ALIGN, "%s", kMsgFirAlign);
+    // always the in-order stream: a search usually follows on what was just written
+    return aeth::fir_exec_on(c->fir, aeth::ctx_stream(f->ctx), hist, in, n, out);
+}
+
+int aeth_corr_exec_levels(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, int kind, float *levels,
+                          size_t n_levels)
+{
+    AETH_REQUIRE(c && c->fir, AETH_E_ARG, "corr is null");
+    AETH_REQUIRE(aeth::level_kind_ok(kind), AETH_E_ARG, "bad level kind %d", kind);
+    AETH_REQUIRE(n_levels == n, AETH_E_LEN, "Levels and samples must have same length");
+    if (n == 0) return AETH_OK;
+    const aeth_fir *f = c->fir;
+    AETH_REQUIRE(in && levels, AETH_E_ARG, "null pointer");
+    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(hist), AETH_E_ALIGN, "%s", kMsgFirAlign);
+    AETH_REQUIRE((reinterpret_cast<uintptr_t>(levels) & 3u) == 0, AETH_E_ALIGN, "levels not 4-byte aligned");
+    AETH_REQUIRE(!touch_bytes(levels, n * sizeof(float), in, n * sizeof(aeth_cf32)) &&
+                 !touch_bytes(levels, n * sizeof(float), hist, (f->ntaps - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
+                 "levels overlaps the input (or its history)");
+    AETH_REQUIRE(f->fft_len >= 1024 && f->fft_len <= 4096, AETH_E_UNSUPPORTED,
+                 "level store: fft_len %zu (one-block-per-workgroup lengths 1024 .. 4096 only)", f->fft_len);
+    FmiArgs a = corr_args(f, hist, in, n);
+    a.levels = levels; a.level_kind = kind;
+    return dispatch_fmi(f->ctx, f->fft_len, a, aeth::ctx_stream(f->ctx));
+}
+
+int aeth_corr_search(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, struct aeth_corr_peak *peaks,
+                     size_t n_peaks, struct aeth_corr_peak *best)
+{
+    AETH_REQUIRE(c && c->fir, AETH_E_ARG, "corr is null");
+    AETH_REQUIRE(peaks || best, AETH_E_ARG, "peaks_dev and best_host are both null: nothing to report");
+    AETH_REQUIRE(n != 0, AETH_E_LEN, "peak of an empty stream");
+    const aeth_fir *f = c->fir;
+    const size_t nblocks = (n + f->hop - 1) / f->hop;
+    AETH_REQUIRE(!peaks || n_peaks == nblocks, AETH_E_LEN, "peaks holds %zu records, the stream has %zu blocks of %zu", n_peaks,
+                 nblocks, f->hop);
+    AETH_REQUIRE(in, AETH_E_ARG, "null pointer");
+    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(hist) && aeth::aligned8(peaks), AETH_E_ALIGN, "%s", kMsgFirAlign);
+    AETH_REQUIRE(!touch_bytes(peaks, nblocks * sizeof(aeth_corr_peak), in, n * sizeof(aeth_cf32)) &&
+                 !touch_bytes(peaks, nblocks * sizeof(aeth_corr_peak), hist, (f->ntaps - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
+                 "peaks overlaps the input (or its history)");
+    AETH_REQUIRE(f->fft_len >= 1024 && f->fft_len <= 4096, AETH_E_UNSUPPORTED,
+                 "peak search: fft_len %zu (one-block-per-workgroup lengths 1024 .. 4096 only)", f->fft_len);
+    AETH_REQUIRE(nblocks < ((size_t)1 << 28), AETH_E_UNSUPPORTED, "peak search: %zu samples", n);
+    aeth_ctx *ctx = f->ctx;
+    aeth::DeviceGuard dev_guard(ctx->device);
+    // slab: [one PeakPart per wave and block | one PeakBest per workgroup of the fold]
+    const int waves = (int)(f->fft_len / 16 / 64);                              // 16 points per lane (aeth_fft_core.h: CfgFor)
+    const size_t nwg = (nblocks + kFoldBlock - 1) / kFoldBlock;
+    const size_t parts_bytes = nblocks * (size_t)waves * sizeof(PeakPart);
+    int rc = corr_slab_ensure(ctx, parts_bytes + nwg * sizeof(PeakBest)); if (rc) return rc;
+    PeakPart *parts = static_cast<PeakPart *>(ctx->corr_slab);
+    PeakBest *wg = reinterpret_cast<PeakBest *>(static_cast<char *>(ctx->corr_slab) + parts_bytes);
+    aeth::HostIO io;
+    if (best) { rc = io.open(ctx, 0, sizeof(aeth_corr_peak)); if (rc) return rc; }   // the pinned bounce buffer
+    hipStream_t s = aeth::ctx_stream(ctx);
+    FmiArgs a = corr_args(f, hist, in, n);
+    a.parts = parts;
+    rc = dispatch_fmi(ctx, f->fft_len, a, s); if (rc) return rc;
+    hipLaunchKernelGGL(corr_fold_kernel, dim3((unsigned)nwg), dim3(kFoldBlock), 0, s, (const PeakPart *)parts, (long long)nblocks,
+                       waves, a.hop, a.ov, n, peaks, wg);
+    if (best)
+        hipLaunchKernelGGL(corr_best_kernel, dim3(1), dim3(kFoldBlock), 0, s, (const PeakBest *)wg, nwg, n,
+                           static_cast<aeth_corr_peak *>(io.buf[1]));
+    AETH_HIP(hipGetLastError());
+    if (best) return io.get(best, 1, sizeof(aeth_corr_peak));
     return AETH_OK;
 }
 

@@ -7,11 +7,22 @@
 
 #include "aeth_internal.h"
 #include "aeth_fft_core.h"
+#include "aeth_levels.h"
 
 namespace aeth {
 namespace firk {
 
 using namespace aeth::fftk;
+
+// V_PEAK: what one wave knows about its share of one block's outputs (16 bytes, one store).  q is -1 and e is
+// kPeakNone when the wave saw no candidate.
+struct __attribute__((aligned(16))) PeakPart {
+    double q;             // largest q(c) (aeth_levels.h) among the wave's samples without a NaN component
+    unsigned e;           // window element of the first sample that has it
+    unsigned nnan;        // samples with a NaN component
+};
+static_assert(sizeof(PeakPart) == 16, "one 16-byte store per wave and block");
+constexpr unsigned kPeakNone = 0x7fffffffu;
 
 struct FmiArgs {
     const cf *in;
@@ -37,6 +48,12 @@ struct FmiArgs {
     cf tab[4] = {};                   // BPSK / QPSK symbol table
     int bps = 0, demod_compat = 0;
     int demod_sep = 0;                // host side only: picks the kernel build (DM_QSEP / DM_QGEN, see demod_block)
+    // V_LEVEL: levels[o] = level of output sample o instead of the sample (aeth_corr_exec_levels)
+    float *levels = nullptr;
+    int level_kind = 0;               // host side only: picks the kernel build (V_LV_DB / V_LV_POWER_DB)
+    // V_PEAK: nothing of the output is stored, every wave leaves one PeakPart per block at parts[blk * waves + wave]
+    // (aeth_corr_search)
+    PeakPart *parts = nullptr;
 };
 
 // Kernel variants (template parameter VAR, a bit set).  0 is the round-1 kernel.
@@ -58,6 +75,9 @@ enum : int {
                     // transform instead of one burst in front of it (the TA command FIFO is full 40 % of the time)
     V_DEMOD = 1024, // product variant: hard demodulation instead of the sample store (aeth_fft_mul_ifft_demod)
     V_DM_BPSK = 1 << 16, V_DM_QGEN = 1 << 17,   // with V_DEMOD: the decision's mode (neither: QPSK, separable table)
+    V_LEVEL = 1 << 19, // product variant: a 4-byte level of every output sample instead of the sample (aeth_corr_exec_levels)
+    V_LV_DB = 1 << 20, V_LV_POWER_DB = 1 << 21,   // with V_LEVEL: the level kind (neither: AETH_LEVEL_NORM)
+    V_PEAK = 1 << 22, // product variant: the block's largest |c|^2 instead of any store (aeth_corr_search)
     V_DMA = 1 << 18, // the next window goes straight into a 16 KiB LDS landing image (buffer_load_dwordx4 ... lds: 8 pieces
                     // of 1 KiB per wave and block instead of 16 register loads) and is read from there at the start of its
                     // own iteration: no prefetch registers, no register copy per block; paid for with ONE exchange image
@@ -71,7 +91,8 @@ enum : int {
 
 // What libaether_hip.so may instantiate; everything else is measurement / diagnosis and builds only where
 // AETH_FIR_LAB is defined non-zero before this header is included (tools/fir_lab.hip)
-constexpr int V_PRODUCT_MASK = V_PRIO | V_XOR | V_SPREAD | V_DECIM | V_DEMOD | V_DM_BPSK | V_DM_QGEN;
+constexpr int V_PRODUCT_MASK = V_PRIO | V_XOR | V_SPREAD | V_DECIM | V_DEMOD | V_DM_BPSK | V_DM_QGEN | V_LEVEL | V_LV_DB |
+                               V_LV_POWER_DB | V_PEAK;
 #ifndef AETH_FIR_LAB
 #define AETH_FIR_LAB 0
 #endif
@@ -324,6 +345,74 @@ __device__ __forceinline__ void demod_block(const cf (&w)[C::P], const FmiArgs &
     }
 }
 
+// The level of every output sample of the block instead of the sample (aeth_levels.h: the arithmetic of
+// aeth_vec_levels, so the values are those of aeth_vec_levels on the stored samples).  Same skeleton as demod_block:
+// a descriptor over the block's valid range, offsets past it for the window elements in front of the valid part, no
+// branch anywhere.
+template <class C, bool SCALED, bool NT, int KIND>
+__device__ __forceinline__ void level_block(const cf (&w)[C::P], const FmiArgs &a, long long blk, int tid)
+{
+    static_assert(C::F == 1, "level store: one block per workgroup");
+    const long long base = blk * a.hop - a.ov;
+    long long left = a.n - base;
+    int bytes = (int)(left < a.frame_n ? left : a.frame_n) * 4;
+    if (blk >= a.nblocks) bytes = 0;
+    auto rs = __builtin_amdgcn_make_buffer_rsrc(a.levels + base, 0, bytes, 0x00020000);
+    const cf ss = mk(a.s_bwd, a.s_bwd);
+#pragma unroll
+    for (int m = 0; m < C::P; m++) {
+        const int e = tid + m * C::T;
+        const int off = (e >= a.ov) ? e * 4 : 0x7ffffff0;
+        const cf v = SCALED ? cscale_k(w[m], ss) : w[m];
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, aeth::level_of<KIND>(v.x, v.y)), rs, off, 0,
+                                              NT ? AETH_FIR_STORE_AUX : 0);
+    }
+}
+
+// The block's peak instead of any sample: the rule of aeth_vec_stats -- order by q (f64), the lowest index wins among
+// equals, a sample with a NaN component is counted and is no candidate.  A lane walks its P elements in ascending
+// index with a strict `>`, so it keeps the first of equals; lanes combine by "larger q, or equal q and lower index",
+// which is associative and commutative: the xor butterfly leaves the same record in every lane of the wave, and the
+// order in which corr_fold_kernel (aeth_fir.hip) combines the waves does not matter either.  One 16-byte record per
+// wave leaves through a descriptor over the block's records (lanes other than 0: offset out of range; a block past the
+// end: zero length) -- no workgroup barrier, no LDS, no atomics.
+template <class C, bool SCALED, bool NT>
+__device__ __forceinline__ void peak_block(const cf (&w)[C::P], const FmiArgs &a, long long blk, int tid)
+{
+    static_assert(C::F == 1 && C::WG % 64 == 0, "peak search: one block per workgroup, whole waves");
+    constexpr int WAVES = C::WG / 64;
+    const long long base = blk * a.hop - a.ov;
+    long long left = a.n - base;
+    const int lim = (int)(left < a.frame_n ? left : a.frame_n);        // window elements at and past it are no outputs
+    const cf ss = mk(a.s_bwd, a.s_bwd);
+    double bq = -1.0;                                                   // q >= 0 for every candidate
+    unsigned be = kPeakNone, nn = 0;
+#pragma unroll
+    for (int m = 0; m < C::P; m++) {
+        const int e = tid + m * C::T;
+        const cf v = SCALED ? cscale_k(w[m], ss) : w[m];
+        const double q = aeth::level_q(v.x, v.y);
+        const bool valid = e >= a.ov && e < lim;
+        nn += (valid && q != q) ? 1u : 0u;                              // q is NaN exactly when a component is
+        const bool take = valid && q > bq;                              // false for a NaN q
+        bq = take ? q : bq; be = take ? (unsigned)e : be;
+    }
+#pragma unroll
+    for (int mask = 32; mask >= 1; mask >>= 1) {
+        const double oq = __shfl_xor(bq, mask);
+        const unsigned oe = __shfl_xor(be, mask);
+        nn += __shfl_xor(nn, mask);
+        const bool take = oq > bq || (oq == bq && oe < be);
+        bq = take ? oq : bq; be = take ? oe : be;
+    }
+    auto rs = __builtin_amdgcn_make_buffer_rsrc(a.parts + blk * WAVES, 0, blk < a.nblocks ? WAVES * 16 : 0, 0x00020000);
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const unsigned long long qb = __builtin_bit_cast(unsigned long long, bq);
+    u32x4 r; r.x = (unsigned)qb; r.y = (unsigned)(qb >> 32); r.z = be; r.w = nn;
+    const int off = (tid & 63) == 0 ? (tid >> 6) * 16 : 0x7ffffff0;
+    __builtin_amdgcn_raw_buffer_store_b128(r, rs, off, 0, NT ? AETH_FIR_STORE_AUX : 0);
+}
+
 // CHECK = false: the caller knows that the block exists (no branch around the stores, so that hipcc keeps
 // counting the memory operations in flight across them)
 template <class C, bool SCALED, bool NT, bool CHECK = true, bool DECIM = false>
@@ -463,6 +552,10 @@ __global__ __launch_bounds__(C::WG, MINW) void fmi_kernel(FmiArgs a)
     static_assert(!(VAR & (V_DM_BPSK | V_DM_QGEN)) || (VAR & V_DEMOD), "decision mode without V_DEMOD");
     [[maybe_unused]] DemodK dk;
     if constexpr (VAR & V_DEMOD) dk = demod_consts<DM>(a);
+    constexpr int LK = (VAR & V_LV_DB) ? AETH_LEVEL_DB : (VAR & V_LV_POWER_DB) ? AETH_LEVEL_POWER_DB : AETH_LEVEL_NORM;
+    static_assert(!(VAR & (V_LV_DB | V_LV_POWER_DB)) || (VAR & V_LEVEL), "level kind without V_LEVEL");
+    static_assert(!(VAR & (V_LEVEL | V_PEAK)) || (C::F == 1 && !BLU && !(VAR & (V_PEEL | V_UNROLL2 | V_DEMOD | V_DECIM))),
+                  "level store / peak search: the plain loop of one-block workgroups");
     unsigned bid = blockIdx.x;
     if constexpr ((VAR & V_XCD) != 0) {
         if ((gridDim.x & 7u) == 0) bid = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
@@ -554,6 +647,8 @@ __global__ __launch_bounds__(C::WG, MINW) void fmi_kernel(FmiArgs a)
 #pragma unroll
             for (int m = 0; m < C::P; m++) asm volatile("" ::"v"(w[m]));
         } else if constexpr (VAR & V_DEMOD) demod_block<C, SCALED, NT, DM>(w, a, dk, blk, tid);
+        else if constexpr (VAR & V_LEVEL) level_block<C, SCALED, NT, LK>(w, a, blk, tid);
+        else if constexpr (VAR & V_PEAK) peak_block<C, SCALED, NT>(w, a, blk, tid);
         else store_block<C, SCALED, NT, true, (VAR & V_DECIM) != 0>(w, a, blk, tid);
     }
     if constexpr (TOUCH) asm volatile("" ::"v"(tprev));

@@ -47,6 +47,9 @@ struct aeth_ctx {
     // per-workgroup partial records of aeth_vec_stats (aeth_stats.hip), grown on demand, released by aeth_ctx_trim
     void *stats_slab = nullptr;
     size_t stats_slab_bytes = 0;
+    // per-wave and per-workgroup records of aeth_corr_search (aeth_fir.hip), grown on demand, released by aeth_ctx_trim
+    void *corr_slab = nullptr;
+    size_t corr_slab_bytes = 0;
 };
 
 namespace aeth {
@@ -68,6 +71,8 @@ int ctx_stage(aeth_ctx *ctx, int i, size_t bytes);
 void fft_cache_release(aeth_ctx *ctx);
 // frees the slab of aeth_vec_stats (aeth_ctx_destroy, aeth_ctx_trim)
 void stats_slab_release(aeth_ctx *ctx);
+// frees the slab of aeth_corr_search (aeth_ctx_destroy, aeth_ctx_trim)
+void corr_slab_release(aeth_ctx *ctx);
 
 // Buffers of one host-slice call (the literal trait call: host slice in, host slice out, synchronous).
 //   small (every buffer <= kZeroCopyMax): the context's two pinned, device-visible bounce buffers -- memcpy in, the kernel

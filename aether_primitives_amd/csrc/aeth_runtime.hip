@@ -255,6 +255,7 @@ int aeth_ctx_destroy(aeth_ctx *ctx)
     (void)hipStreamSynchronize(aeth::ctx_stream(ctx));
     aeth::fft_cache_release(ctx);
     aeth::stats_slab_release(ctx);
+    aeth::corr_slab_release(ctx);
     overlap_release(ctx);
     aeth::pipe_release(ctx);
     for (int i = 0; i < 2; i++) {

@@ -48,6 +48,7 @@ typedef struct { float re, im; } aeth_cf32;
 typedef struct aeth_ctx aeth_ctx;       /* device + stream + staging buffers      */
 typedef struct aeth_fft aeth_fft;       /* replaces Cfft (src/fft.rs:134-159)     */
 typedef struct aeth_fir aeth_fir;       /* gives Fir<T> (src/fir.rs:3-22) a body  */
+typedef struct aeth_corr aeth_corr;     /* streaming correlator: a matched filter with fused level / peak stores */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -303,6 +304,54 @@ AETH_API int aeth_fir_exec_decim(aeth_fir *fir, const aeth_cf32 *hist_dev, const
                                  aeth_cf32 *out_dev, size_t n_out);
 AETH_API int aeth_fir_exec_host(aeth_fir *fir, const aeth_cf32 *hist_host, const aeth_cf32 *in_host,
                                 size_t n, aeth_cf32 *out_host);
+
+/* ---- streaming correlator (listed as open in the reference) ------------------------------------ */
+/* The reference lists "Add Correlation by Freq. Domain Convolution" as an open item (README.md:95); what it has is the
+ * chain of its "correlator inplace" benchmark (benches/benches.rs:394-416), a circular correlation inside one frame --
+ * aeth_fft_mul_ifft.  Run as overlap-save over a stream, that chain finds a template s of M = nref samples in x:
+ *
+ *     c[j] = sum_{k<M} conj(s[M-1-k]) * x[j-k]        j = 0 .. n-1
+ *
+ * the causal matched filter: exactly aeth_fir_exec with taps h[k] = conj(s[M-1-k]).  x[i] for i < 0 is zero, or comes
+ * from hist_dev (the M-1 samples in front of in_dev[0]), as for the FIR.  An occurrence of s that starts at stream index
+ * p peaks at j = p + M - 1, so lag = j - (M-1); with a history the lag can be as low as -(M-1).  Normalised
+ * correlation (division by the local energy) is not computed.
+ *
+ * The object holds the filter built from the conj-reversed template and nothing else; create takes the length rules
+ * and error codes of aeth_fir_create (fft_len a power of two in [2, 4096], fft_len >= 2*nref).  All three exec calls are
+ * ordered on the context's in-order stream (never on the overlap lane) and validate everything before any device work. */
+AETH_API int aeth_corr_create(aeth_ctx *ctx, const aeth_cf32 *ref_host, size_t nref, size_t fft_len, aeth_corr **out);
+AETH_API int aeth_corr_destroy(aeth_corr *corr);
+AETH_API size_t aeth_corr_nref(const aeth_corr *corr);
+AETH_API size_t aeth_corr_fft_len(const aeth_corr *corr);
+AETH_API size_t aeth_corr_hop(const aeth_corr *corr);     /* outputs per overlap-save block = samples per peak record */
+/* out_dev[j] = c[j].  Any fft_len the FIR supports; bit-identical to aeth_fir_exec with the taps above, and refuses what
+ * it refuses (output overlapping the input or the history: AETH_E_ARG; alignment: AETH_E_ALIGN) with the same texts. */
+AETH_API int aeth_corr_exec(aeth_corr *corr, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
+                            aeth_cf32 *out_dev);
+/* levels_dev[j] = level of c[j] (level kinds: see aeth_vec_levels).  Every overlap-save block stores a 4-byte level
+ * where the 8-byte sample would go; c is never written: 8 B read + 4 B written per sample.  All three kinds are ONE pass
+ * (the f64 logarithm of the two dB kinds runs in the fused kernel's registers).  Bit-identical to aeth_corr_exec into a
+ * scratch buffer followed by aeth_vec_levels.  n_levels != n -> AETH_E_LEN; levels_dev 4-byte aligned (AETH_E_ALIGN) and
+ * clear of the input and the history (AETH_E_ARG).  fft_len 1024 .. 4096 (AETH_E_UNSUPPORTED otherwise). */
+AETH_API int aeth_corr_exec_levels(aeth_corr *corr, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
+                                   int level_kind, float *levels_dev, size_t n_levels);
+/* Peak search in one pass: nothing of c goes to memory (8 B read per sample + 16 B written per block).  One record
+ * per overlap-save block b, covering the outputs [b*hop, min((b+1)*hop, n)), under the rule of aeth_vec_stats:
+ *   index  GLOBAL output index of the largest q(c[j]) of the block; the LOWEST index wins among equal q; a sample with
+ *          a NaN component is no candidate
+ *   norm   norm() of that sample
+ *   n_nan  samples of the block with a NaN component
+ * A block without a candidate reports index = n and norm = NaN.  16 bytes, no padding. */
+struct aeth_corr_peak { size_t index; float norm; unsigned n_nan; };
+/* peaks_dev (DEVICE memory, 8-byte aligned, clear of the input and the history) may be NULL; if it is not, n_peaks must
+ * be ceil(n / hop) (AETH_E_LEN).  best_host may be NULL; if it is not, the call waits and returns the best record of the
+ * whole stream under the same ordering with n_nan summed (saturating at UINT32_MAX).  Both NULL -> AETH_E_ARG; n == 0 ->
+ * AETH_E_LEN.  The records equal aeth_vec_stats (max_index, max_norm, n_nan) of the matching slice of aeth_corr_exec's
+ * output.  No floating-point atomics anywhere: bitwise reproducible from run to run.  fft_len 1024 .. 4096
+ * (AETH_E_UNSUPPORTED otherwise).  The call's internal records live in the context (released by aeth_ctx_trim). */
+AETH_API int aeth_corr_search(aeth_corr *corr, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
+                              struct aeth_corr_peak *peaks_dev, size_t n_peaks, struct aeth_corr_peak *best_host);
 
 /* ---- pinned host buffers: src/pool.rs:43-221 -------------------------------------------------- */
 /* The reference's object pool ("useful for large buffers and other time expensive objects", :9-10) with pinned

@@ -407,6 +407,53 @@ private:
     aeth_fir *h_ = nullptr;
 };
 
+// ---- streaming correlator (the reference's open item "Add Correlation by Freq. Domain Convolution", README.md:95) ----
+// c[j] = sum_k conj(ref[M-1-k]) * x[j-k]: an occurrence of ref that starts at p peaks at j = p + M - 1
+using CorrPeak = struct ::aeth_corr_peak;     // the record of aeth_corr_search, field for field
+class Corr {
+public:
+    Corr(Context &ctx, const std::vector<cf32> &ref, size_t fft_len = 2048) { check(aeth_corr_create(ctx.get(), raw(ref.data()), ref.size(), fft_len, &h_)); }
+    ~Corr() { aeth_corr_destroy(h_); }
+    Corr(const Corr &) = delete;
+    Corr &operator=(const Corr &) = delete;
+    size_t nref() const { return aeth_corr_nref(h_); }
+    size_t fft_len() const { return aeth_corr_fft_len(h_); }
+    size_t hop() const { return aeth_corr_hop(h_); }
+    size_t n_blocks(size_t n) const { return (n + hop() - 1) / hop(); }
+    void correlate(const DeviceVec &x, DeviceVec &c, const DeviceVec *hist = nullptr)
+    {
+        if (c.len() != x.len()) throw Panic(AETH_E_LEN, "Vectors must have same length");
+        check(aeth_corr_exec(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), c.ptr()));
+    }
+    // the level of every c[j] in one pass (c is never written)
+    DeviceF32 levels(const DeviceVec &x, int kind = AETH_LEVEL_NORM, const DeviceVec *hist = nullptr)
+    {
+        DeviceF32 out(x.ctx(), x.len());
+        check(aeth_corr_exec_levels(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), kind, out.ptr(), out.len()));
+        return out;
+    }
+    // the best peak of the stream in one pass; `blocks` (optional) receives one record per hop() outputs
+    CorrPeak search(const DeviceVec &x, std::vector<CorrPeak> *blocks = nullptr, const DeviceVec *hist = nullptr)
+    {
+        CorrPeak best{};
+        const aeth_cf32 *hp = hist ? hist->ptr() : nullptr;
+        if (!blocks) { check(aeth_corr_search(h_, hp, x.ptr(), x.len(), nullptr, 0, &best)); return best; }
+        const size_t nb = n_blocks(x.len());
+        void *dev = nullptr;
+        check(aeth_dev_alloc(x.ctx().get(), (nb ? nb : 1) * sizeof(CorrPeak), &dev));
+        int rc = aeth_corr_search(h_, hp, x.ptr(), x.len(), static_cast<CorrPeak *>(dev), nb, &best);
+        blocks->resize(nb);
+        if (rc == AETH_OK && nb) rc = aeth_download(x.ctx().get(), blocks->data(), dev, nb * sizeof(CorrPeak));
+        aeth_dev_free(x.ctx().get(), dev);
+        check(rc);
+        return best;
+    }
+    aeth_corr *get() const { return h_; }
+
+private:
+    aeth_corr *h_ = nullptr;
+};
+
 // ---- pipeline (src/pipeline.rs:24-41 add_stage, :123-137 new, :89-114 the per-stage report) ------------------
 // The reference chains closures over channels; the device pipeline has five fixed stages (copy-in | upload | compute |
 // download | copy-out) and the compute stage is one of the library's ops:

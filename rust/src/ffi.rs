@@ -1,11 +1,12 @@
 //! `extern "C"` declarations: one to one with include/aether_hip.h.
 #![allow(non_camel_case_types)]
 use aether_primitives::cf32;
-use std::os::raw::{c_char, c_float, c_int, c_void};
+use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
 
 #[repr(C)] pub struct aeth_ctx { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_fft { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_fir { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_corr { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
 pub const AETH_POOL_ZERO_ON_RETURN: c_int = 1;
@@ -23,6 +24,10 @@ pub const AETH_VEC_ADD: c_int = 4; pub const AETH_VEC_SUB: c_int = 5; pub const 
 #[derive(Clone, Copy, Debug, Default)]
 pub struct aeth_vec_stats_t { pub n: usize, pub n_nan: usize, pub min_index: usize, pub max_index: usize, pub min_norm: c_float,
                               pub max_norm: c_float, pub mean_re: f64, pub mean_im: f64, pub power: f64 }
+/// aeth_corr_peak: one record of aeth_corr_search (16 bytes, no padding)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct aeth_corr_peak { pub index: usize, pub norm: c_float, pub n_nan: c_uint }
 pub const AETH_LEVEL_NORM: c_int = 0; pub const AETH_LEVEL_DB: c_int = 1; pub const AETH_LEVEL_POWER_DB: c_int = 2;
 /// aeth_stream_op: the compute stage of the host pipeline (src/pipeline.rs:24-41 takes a closure; a closure cannot
 /// cross the C ABI, so the stage is one of the library's device ops, described field by field as in aether_hip.h)
@@ -142,6 +147,18 @@ extern "C" {
     pub fn aeth_fir_ntaps(fir: *const aeth_fir) -> usize;
     pub fn aeth_fir_fft_len(fir: *const aeth_fir) -> usize;
     pub fn aeth_fir_hop(fir: *const aeth_fir) -> usize;
+    // streaming correlator: c[j] = sum_k conj(s[M-1-k]) * x[j-k] (the reference's open item, README.md:95)
+    pub fn aeth_corr_create(ctx: *mut aeth_ctx, reference: *const cf32, nref: usize, fft_len: usize,
+                            out: *mut *mut aeth_corr) -> c_int;
+    pub fn aeth_corr_destroy(corr: *mut aeth_corr) -> c_int;
+    pub fn aeth_corr_nref(corr: *const aeth_corr) -> usize;
+    pub fn aeth_corr_fft_len(corr: *const aeth_corr) -> usize;
+    pub fn aeth_corr_hop(corr: *const aeth_corr) -> usize;
+    pub fn aeth_corr_exec(corr: *mut aeth_corr, hist: *const cf32, inp: *const cf32, n: usize, out: *mut cf32) -> c_int;
+    pub fn aeth_corr_exec_levels(corr: *mut aeth_corr, hist: *const cf32, inp: *const cf32, n: usize, level_kind: c_int,
+                                 levels: *mut c_float, n_levels: usize) -> c_int;
+    pub fn aeth_corr_search(corr: *mut aeth_corr, hist: *const cf32, inp: *const cf32, n: usize, peaks: *mut aeth_corr_peak,
+                            n_peaks: usize, best: *mut aeth_corr_peak) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;
