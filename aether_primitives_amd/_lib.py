@@ -71,6 +71,7 @@ PROTOTYPES = {
     "aeth_fft_destroy": (i32, [vp]),
     "aeth_fft_len": (sz, [vp]),
     "aeth_fft_algorithm": (C.c_char_p, [vp]),
+    "aeth_fft_route": (C.c_char_p, [vp]),
     "aeth_fft_exec": (i32, [vp, vp, sz, vp, sz, i32, i32, f32]),
     "aeth_fft_exec_mirrored": (i32, [vp, vp, sz, vp, sz, i32, i32, f32]),
     "aeth_fft_exec_interpolate": (i32, [vp, vp, sz, sz, i32, i32, f32, vp, sz, sz, i32, psz]),

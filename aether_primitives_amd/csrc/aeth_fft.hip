@@ -31,6 +31,7 @@
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -682,7 +683,7 @@ bool factorize_mixed(size_t n, std::vector<int> &fac)
 // len = n1 * n2, both factors at most 8192 and served by a single-workgroup kernel; the pair nearest the square
 // root whose factors are both register-resident (power of two or in the ragged table), else the nearest pair the
 // LDS mixed-radix kernel can do.
-bool split_fourstep_mixed(size_t len, size_t *n1, size_t *n2)
+bool split_fourstep_mixed(size_t len, size_t *n1, size_t *n2, int *kind)
 {
     auto fast = [](size_t n) { return (is_pow2(n) && n <= 8192) || aeth::fft_ragged_supported(n); };
     // a small first factor over one register-resident transform (up to 20480 points): no transposes.  The batched
@@ -694,7 +695,7 @@ bool split_fourstep_mixed(size_t len, size_t *n1, size_t *n2)
         for (size_t r = 2; r <= 16; r++) {
             if (!aeth::fourstep_small_factor(r) || len % r) continue;
             if (pass == 0 && len / r > pref) continue;
-            if (fast(len / r)) { *n1 = r; *n2 = len / r; return true; }
+            if (fast(len / r)) { *n1 = r; *n2 = len / r; *kind = aeth::FFT_SPLIT_SMALL; return true; }
         }
     size_t root = 1;
     while ((root + 1) * (root + 1) <= len) root++;
@@ -704,11 +705,31 @@ bool split_fourstep_mixed(size_t len, size_t *n1, size_t *n2)
         if (len % a) continue;
         const size_t b = len / a;
         if (b > 8192) break;
-        if (fast(a) && fast(b)) { *n1 = a; *n2 = b; return true; }
+        if (fast(a) && fast(b)) { *n1 = a; *n2 = b; *kind = aeth::FFT_SPLIT_FAST; return true; }
         if (!fb1 && (fast(a) || factorize_mixed(a, fac)) && (fast(b) || factorize_mixed(b, fac))) { fb1 = a; fb2 = b; }
     }
-    if (fb1) { *n1 = fb1; *n2 = fb2; return true; }
+    if (fb1) { *n1 = fb1; *n2 = fb2; *kind = aeth::FFT_SPLIT_FALLBACK; return true; }
     return false;
+}
+
+// aeth_fft_route (grammar: include/aether_hip.h); every sub-plan came out of aeth_fft_create and has its own
+std::string describe_route(const aeth_fft *p)
+{
+    const std::string name = p->algo_name, len = std::to_string(p->len);
+    switch (p->algo) {
+    case aeth::FFT_ALGO_FOURSTEP:
+        if (p->n2 > 4096) return name + " deep " + std::to_string(p->n1) + "x[" + p->sub2->route + "]";
+        return name + " " + std::to_string(p->n1) + "x" + std::to_string(p->n2);
+    case aeth::FFT_ALGO_FOURSTEP_MIXED:
+        // a first factor in registers has no sub-plan (fft_plan_fourstep_mixed), whichever branch of the split found it
+        if (p->split_kind == aeth::FFT_SPLIT_SMALL || !p->sub1) return name + "[small " + std::to_string(p->n1) + " | " + p->sub2->route + "]";
+        return name + (p->split_kind == aeth::FFT_SPLIT_FAST ? "[fast " : "[fallback ") + p->sub1->route + " x " + p->sub2->route + "]";
+    case aeth::FFT_ALGO_BLUESTEIN:
+        if (aeth::bluestein_one_launch(p)) return name + " " + len + " (one launch, M=" + std::to_string(p->blu_m) + ")";
+        return name + " " + len + " (multi launch, M=" + std::to_string(p->blu_m) + ")[" + p->blu_sub->route + "]";
+    default:
+        return name + " " + len;
+    }
 }
 
 int make_twiddles(aeth_ctx *ctx, size_t n, float2 **out_dev)
@@ -829,7 +850,7 @@ int aeth_fft_create(aeth_ctx *ctx, size_t len, size_t max_batch, aeth_fft **out)
         p->algo = aeth::FFT_ALGO_FOURSTEP;
         p->algo_name = "fourstep_pow2";
         rc = aeth::fft_plan_fourstep(p);
-    } else if (!aeth::lab_int("AETH_FFT_NO4SMIXED", 0) && split_fourstep_mixed(len, &p->n1, &p->n2)) {
+    } else if (!aeth::lab_int("AETH_FFT_NO4SMIXED", 0) && split_fourstep_mixed(len, &p->n1, &p->n2, &p->split_kind)) {
         p->algo = aeth::FFT_ALGO_FOURSTEP_MIXED;
         p->algo_name = "fourstep_mixed";
         rc = aeth::fft_plan_fourstep_mixed(p);
@@ -846,7 +867,8 @@ int aeth_fft_create(aeth_ctx *ctx, size_t len, size_t max_batch, aeth_fft **out)
     // through it, and the sub-plans of the four-step / chirp-z paths and the FIR's plan never do (a 2^24-point child
     // would otherwise hold 256 MiB of device and 256 MiB of pinned host memory for nothing)
     (void)max_batch;
-    if (rc != AETH_OK) { aeth_fft_destroy(p); return rc; }
+    if (rc != AETH_OK) { aeth_fft_destroy(p); return rc; }        // sub-plans, chirps and tables included
+    p->route = describe_route(p);
     *out = p;
     return AETH_OK;
 }
@@ -934,6 +956,7 @@ int aeth_host_vec_fft(aeth_ctx *ctx, aeth_cf32 *x_host, size_t n, int sign, int 
 
 size_t aeth_fft_len(const aeth_fft *p) { return p ? p->len : 0; }
 const char *aeth_fft_algorithm(const aeth_fft *p) { return p ? p->algo_name : ""; }
+const char *aeth_fft_route(const aeth_fft *p) { return p ? p->route.c_str() : ""; }
 
 // device temp of >= elems and (host = true) the pinned 2*len mirror tfwd/tbwd lend out
 static int ensure_temps(aeth_fft *p, size_t elems, bool host)

@@ -488,6 +488,9 @@ int fft_run_fourstep_mixed(aeth_fft *plan, const float2 *in, float2 *out, size_t
         int rc = ensure_work(plan, total);
         if (rc) return rc;
         switch (n1) {
+        // no shipped plan has n1 = 2 (kept for the lab build's AETH_4SM_PREF_M): split_fourstep_mixed takes 2 only when
+        // len / 2 is register-resident, and then len is a power of two, a table row or a stockham_mixed length, or the
+        // first pass finds 5, 6 or 10 first (the argument in full: ALLOWLIST of tools/variant_coverage.py)
         case 2: return run_small_first_factor<2>(plan, in, out, batch, sign, scale);
         case 3: return run_small_first_factor<3>(plan, in, out, batch, sign, scale);
         case 4: return run_small_first_factor<4>(plan, in, out, batch, sign, scale);
@@ -532,6 +535,11 @@ int fft_plan_bluestein(aeth_fft *plan)
             if (aeth::fft_ragged_supported(m)) { M = m; break; }
     }
     plan->blu_m = M;
+    // the convolution is a plan of its own, so M shares the limit of every length: N in (2^23, 2^24] that got here
+    // (no power of two, no split into two single-launch factors) would need M = 2^25
+    if (M > ((size_t)1 << 24))
+        return set_error(AETH_E_UNSUPPORTED, "FFT length %zu: above 2^23 only 2^24 and products of two single-launch lengths of at most 8192 points "
+                         "are served (the chirp-z transform of this one needs a convolution of %zu > 2^24 points)", N, M);
     int rc = aeth_fft_create(plan->ctx, M, 1, &plan->blu_sub);
     if (rc) return rc;
     // chirp[k] = exp(-j pi k^2 / N), k^2 reduced mod 2N in integers to keep the angle exact
@@ -559,10 +567,12 @@ int fft_plan_bluestein(aeth_fft *plan)
     return aeth_ctx_sync(plan->ctx);
 }
 
+bool bluestein_one_launch(const aeth_fft *plan) { return plan->blu_sub && plan->blu_sub->algo == FFT_ALGO_POW2 && plan->blu_m <= 4096; }
+
 int fft_run_bluestein(aeth_fft *plan, const float2 *in, float2 *out, size_t batch, int sign, float scale)
 {
     const size_t N = plan->len, M = plan->blu_m;
-    if (plan->blu_sub->algo == FFT_ALGO_POW2 && M <= 4096 && N * batch < 0x7fffffffull)
+    if (bluestein_one_launch(plan) && N * batch < 0x7fffffffull)
         // the whole chirp-z chain in one launch; DFT+(x) = conj(DFT-(conj x)) by conjugating on the way in and out
         return fmi_bluestein(plan->blu_sub, in, out, N, batch, plan->blu_chirp, plan->blu_filt, sign > 0 ? 1 : 0, scale);
     int rc = ensure_work(plan, M * batch);

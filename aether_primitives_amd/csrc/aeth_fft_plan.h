@@ -4,6 +4,7 @@
 
 #include "aeth_internal.h"
 
+#include <string>
 #include <vector>
 
 struct aeth_fft {
@@ -11,6 +12,7 @@ struct aeth_fft {
     size_t len = 0;
     int algo = 0;
     const char *algo_name = "";
+    std::string route;               // aeth_fft_route: the plan described recursively, sub-plans included
     float2 *tw_dev = nullptr;        // exp(-2 pi i k / len), k < len
     float2 *tw_lane_dev = nullptr;   // stockham_pow2: per-lane twiddle registers, [slot][lane]
     float2 *tw_pass_dev = nullptr;   // stockham_mixed: per-pass twiddles, contiguous in the butterfly index
@@ -20,6 +22,7 @@ struct aeth_fft {
     std::vector<int> factors;        // stockham_mixed radix schedule
     // fourstep_pow2: len = n1 * n2
     size_t n1 = 0, n2 = 0;
+    int split_kind = 0;              // fourstep_mixed: which branch of the split chose n1, n2 (FFT_SPLIT_*)
     aeth_fft *sub1 = nullptr, *sub2 = nullptr;   // the N1- and N2-point plans (per-lane twiddle tables)
     float2 *work_dev = nullptr;      // intermediate of the two launches (len * batch)
     size_t work_elems = 0;
@@ -45,6 +48,7 @@ struct aeth_corr {
 
 namespace aeth {
 
+enum { FFT_SPLIT_SMALL = 1, FFT_SPLIT_FAST = 2, FFT_SPLIT_FALLBACK = 3 };
 enum { FFT_ALGO_POW2 = 1, FFT_ALGO_MIXED = 2, FFT_ALGO_FOURSTEP = 3, FFT_ALGO_BLUESTEIN = 4, FFT_ALGO_RAGGED = 5, FFT_ALGO_FOURSTEP_MIXED = 6 };
 
 int fft_run(aeth_fft *plan, const float2 *in, float2 *out, size_t batch, int sign, float scale);
@@ -52,6 +56,7 @@ int fft_ensure_tmp(aeth_fft *plan, size_t elems);
 
 int fft_plan_fourstep(aeth_fft *plan);
 int fft_run_fourstep(aeth_fft *plan, const float2 *in, float2 *out, size_t batch, int sign, float scale);
+bool bluestein_one_launch(const aeth_fft *plan);  // the whole chirp-z chain in one kernel (batches below 2^31 samples)
 bool fourstep_small_factor(size_t r);             // first factors the transpose-free path handles in registers
 int fft_plan_fourstep_mixed(aeth_fft *plan);     // n1, n2 set by the caller
 int fft_run_fourstep_mixed(aeth_fft *plan, const float2 *in, float2 *out, size_t batch, int sign, float scale);

@@ -77,6 +77,11 @@ class HipFft:
     def algorithm(self):
         return self._lib.aeth_fft_algorithm(self.h).decode()
 
+    @property
+    def route(self):
+        """the plan with its sub-plans as text (grammar: include/aether_hip.h, aeth_fft_route)"""
+        return self._lib.aeth_fft_route(self.h).decode()
+
     # ---- generic exec with explicit sign (the C ABI's shape) ----
     def exec(self, inp, out, sign, s=Scale.NONE):
         if _is_dev(inp):

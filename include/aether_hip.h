@@ -216,12 +216,36 @@ AETH_API int aeth_scale_apply(aeth_ctx *ctx, int scale_kind, float x, aeth_cf32 
 
 /* ---- Fft: trait Fft src/fft.rs:48-77, struct Cfft :134-235 ----------------- */
 /* Cfft::with_len(len) (:147-158).  max_batch sizes the plan's device scratch
- * (>= 2*len*max_batch, mirroring Cfft.tmp :141,155); exec grows it on demand. */
+ * (>= 2*len*max_batch, mirroring Cfft.tmp :141,155); exec grows it on demand.
+ * Lengths: every len from 1 to 2^23, and of the lengths in (2^23, 2^24] the power of two 2^24 and every product
+ * n1 * n2 of two factors of at most 8192 points that one launch each transforms (a power of two, a row of the
+ * register-resident table, or a length the LDS mixed-radix kernel does: prime factors all <= 61 in at most 16 radix passes).  Any other length takes the chirp-z
+ * transform, whose convolution of M >= 2 len - 1 points (a power of two) is a plan of its own under the same limit;
+ * above 2^23 that would be M = 2^25, and the call returns AETH_E_UNSUPPORTED with a message that names len (8388609
+ * and 16777213 are such lengths; 9000000 = 3000 * 3000 is served).  len > 2^24 -> AETH_E_UNSUPPORTED.  Nothing stays
+ * allocated after a refusal.  aeth_vec_fft, aeth_host_vec_fft and the host flavours plan through this call. */
 AETH_API int aeth_fft_create(aeth_ctx *ctx, size_t len, size_t max_batch, aeth_fft **out);
 AETH_API int aeth_fft_destroy(aeth_fft *plan);
 AETH_API size_t aeth_fft_len(const aeth_fft *plan);                                   /* Fft::len :232-234 */
 /* text name of the kernel path chosen for this length ("stockham_pow2", ...) */
 AETH_API const char *aeth_fft_algorithm(const aeth_fft *plan);
+/* the whole plan, sub-plans included, as text owned by the plan (valid until aeth_fft_destroy); "" for a null plan.
+ *   route  := leaf | four | mixed | chirp
+ *   leaf   := ("identity" | "stockham_pow2" | "stockham_mixed" | "stockham_mixed_ragged") " " len
+ *   four   := "fourstep_pow2 " n1 "x" n2                      two launches: n1-point columns, n2-point rows
+ *           | "fourstep_pow2 deep " n1 "x[" route "]"          the rows are a plan of their own (2^23, 2^24)
+ *   mixed  := "fourstep_mixed[small " n1 " | " route "]"       n1 in 2..10, 12, 15, 16 in registers over one
+ *                                                              register-resident transform of len / n1: no transposes
+ *           | "fourstep_mixed[fast " route " x " route "]"     the pair nearest the square root whose factors are both
+ *                                                              register-resident (power of two or table row)
+ *           | "fourstep_mixed[fallback " route " x " route "]" else the nearest pair of single-launch factors
+ *   chirp  := "bluestein " len " (one launch, M=" m ")"        the chirp-z chain in one kernel (m <= 4096; a call of
+ *                                                              2^31 samples or more takes the multi-launch form)
+ *           | "bluestein " len " (multi launch, M=" m ")[" route "]"   pre, transform, multiply, inverse, post; the
+ *                                                              route is that of the m-point convolution transform
+ * e.g. "fourstep_mixed[fallback bluestein 82 (one launch, M=256) x stockham_mixed_ragged 100]",
+ *      "bluestein 2097153 (multi launch, M=8388608)[fourstep_pow2 deep 128x[fourstep_pow2 256x256]]". */
+AETH_API const char *aeth_fft_route(const aeth_fft *plan);
 /* `batch` frames of len() each, device pointers, out == in => in-place
  * (fwd/bwd :162-182, ifwd/ibwd :184-204).  n_in is the TOTAL element count of
  * `in` and must equal batch*len ("Input and FFT must be the same length"). */

@@ -119,6 +119,7 @@ extern "C" {
     pub fn aeth_fft_destroy(plan: *mut aeth_fft) -> c_int;
     pub fn aeth_fft_len(plan: *const aeth_fft) -> usize;
     pub fn aeth_fft_algorithm(plan: *const aeth_fft) -> *const c_char;
+    pub fn aeth_fft_route(plan: *const aeth_fft) -> *const c_char;
     pub fn aeth_fft_exec_tmp(plan: *mut aeth_fft, inp: *const cf32, n_in: usize, batch: usize, sign: c_int,
                              scale_kind: c_int, x: c_float, view: *mut *const cf32) -> c_int;
     pub fn aeth_fft_exec(plan: *mut aeth_fft, inp: *const cf32, n_in: usize, out: *mut cf32, batch: usize,

@@ -10,7 +10,7 @@ same order): a kernel is a FUNC symbol that has a `<name>.kd` descriptor beside 
 command, children included).  The report has four groups:
     dispatched                              library kernels the run launched (with the launch count)
     never dispatched                        library kernels the run did not launch, outside the allowlist
-    never dispatched, allowlisted           the same, named in ALLOWLIST below with the reason no test reaches them
+    never dispatched, allowlisted           the same, named in ALLOWLIST below with the reason no run can reach them
     dispatched, not in the library         a sanity check of the name matching (the HIP runtime's own copy and fill kernels land here)
 --check exits 1 when a kernel of one of the CHECKED families is in the second group.
 """
@@ -30,9 +30,12 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 LIB = os.path.join(ROOT, "aether_primitives_amd", "lib", "libaether_hip.so")
 
 # Families whose every instantiation must be dispatched by the suite or allowlisted (--check): the fused
-# FFT*H*IFFT kernel, the element-wise kernels, the modulation kernels and the streamed power-of-two FFT.
+# FFT*H*IFFT kernel, the element-wise kernels, the modulation kernels, the streamed power-of-two FFT and every kernel
+# of the large-FFT planner's routes (tests/test_gpu_fft_routes.py).
 CHECKED = ("fmi_kernel", "chain_kernel", "ew_kernel", "modulate_kernel", "modulate_generic_kernel",
-           "modulate_awgn_kernel", "demod_kernel", "demod_generic_kernel", "fft_pow2_stream_kernel")
+           "modulate_awgn_kernel", "demod_kernel", "demod_generic_kernel", "fft_pow2_stream_kernel",
+           "smallcol_kernel", "interleave_kernel", "transpose_kernel", "blu_pre", "blu_post", "blu_mul",
+           "fourstep_rows", "fourstep_cols", "fft_ragged_kernel")
 
 # (regex on the short name, why no test of `pytest -m gpu` reaches it).  "Not tested" is not a reason.
 ALLOWLIST = [
@@ -44,6 +47,32 @@ ALLOWLIST = [
     # serve, and every length up to 16 is served by one of them, so the one-launch convolution is never shorter than 64
     (r"^fmi_kernel<Cfg<(2|4|8|16|32), [^>]*>, true, 1, (true|false), true, 0>",
      "unreachable: chirp-z lengths start at 17 (2..16 are power-of-two or ragged rows), so M = pow2 >= 2n-1 >= 64"),
+    # unreachable: split_fourstep_mixed (aeth_fft.hip) takes R = 2 only when len / 2 is register-resident.  len / 2 a
+    # power of two makes len one (fourstep_pow2 or the single-workgroup kernels).  len / 2 a table row of at most 4096
+    # points makes len <= 8192 with prime factors up to 23 (stockham_mixed, or a row itself).  The rows above 4096 are
+    # the 5-smooth lengths up to 20480, so len is 5-smooth too: up to 20480 it is a row itself, and in (20480, 40960]
+    # the first pass over the factors (rows of at most 8192 points) skips R = 2 and finds 5 or 10 (5 | len) or 6
+    # (3 | len) before the second pass would try R = 2.  A brute-force mirror of the planner agrees for every length
+    # up to 400000.
+    (r"^(smallcol_kernel<2, |interleave_kernel<2, )",
+     "unreachable: no length plans a first factor 2 (len / 2 register-resident makes len a power of two, a table "
+     "row, a stockham_mixed length, or a length whose first pass finds R = 5, 6 or 10)"),
+    # fourstep_pow2 (fft_plan_fourstep, aeth_fft_big.hip) splits 2^15 ... 2^24 into n1 = 128 (2^15, 2^23), 256 (2^16 ...
+    # 2^19, 2^24), 512, 1024, 2048 (2^20 ... 2^22) columns over rows of n2 = 256 (2^15, 2^16), 512, 1024, 2048 (2^19 ...
+    # 2^22) points or of 65536 (2^23, 2^24: a plan of their own, no row kernel).  AETH_POW2_SWITCH instantiates every
+    # power of two 2 ... 4096 all the same; the other splits need AETH_4S_N1LOG / AETH_4S_DEEP_FROM, knobs of the lab build
+    (r"^fourstep_cols<Cfg<(2|4|8|16|32|64|4096), ",
+     "unreachable: fourstep_pow2 plans 128 ... 2048 columns only (other splits: AETH_4S_N1LOG, lab build)"),
+    (r"^fourstep_rows<Cfg<(2|4|8|16|32|64|128|4096), ",
+     "unreachable: fourstep_pow2 plans rows of 256 ... 2048 points, or 65536 as a sub-plan (other splits: AETH_4S_N1LOG, lab build)"),
+    # launch_cols picks ONE column-group build per n1: 32 columns per workgroup where 32 * T lanes fit 1024 (n1 = 128,
+    # 256), else 16; the ternary that picks it instantiates all three builds for every n1
+    (r"^fourstep_cols<Cfg<(128|256), .*, 16, 1024>$",
+     "lab-only: n1 <= 256 takes the 32-column build; the 16-column one runs under AETH_4S_COLG < 32 (lab build) only"),
+    (r"^fourstep_cols<Cfg<(512|1024|2048), .*, 32, 1024>$",
+     "unreachable: 32 columns of n1 >= 512 points exceed 1024 lanes (col_group_of < 32), so launch_cols never picks this build"),
+    (r"^fourstep_cols<.*, 16, 512>$",
+     "lab-only: the 512-lane column build runs under AETH_4S_MAXL <= 512 (lab build) only"),
 ]
 
 # families with this many instantiations or more are summarised by count unless --full (the ragged FFT: one
