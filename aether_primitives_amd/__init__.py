@@ -20,6 +20,8 @@ from .corr import Corr, CorrPeak                          # noqa: E402
 from . import sampling                                    # noqa: E402
 from . import modulation                                  # noqa: E402
 from . import noise                                       # noqa: E402
+from . import sequence                                    # noqa: E402
+from .sequence import Sequence, lte_gold                  # noqa: E402
 from . import file                                        # noqa: E402
 from . import pool                                        # noqa: E402
 from . import pipeline                                    # noqa: E402
@@ -27,4 +29,5 @@ from .evm import assert_evm, evm_db                       # noqa: E402
 
 __all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "DeviceF32", "HostVec", "VecStats", "LEVEL_NORM",
            "LEVEL_DB", "LEVEL_POWER_DB", "Scale", "HipFft",
-           "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "Corr", "CorrPeak", "sampling", "modulation", "noise", "assert_evm", "evm_db"]
+           "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "Corr", "CorrPeak", "sampling", "modulation", "noise", "sequence", "Sequence",
+           "lte_gold", "assert_evm", "evm_db"]

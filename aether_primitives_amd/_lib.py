@@ -21,6 +21,13 @@ E_LEN, E_ARG, E_ALIGN, E_HIP, E_NOMEM, E_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 vp, sz, f32, i32 = C.c_void_p, C.c_size_t, C.c_float, C.c_int
 pvp = C.POINTER(C.c_void_p)
 psz = C.POINTER(C.c_size_t)
+u64 = C.c_uint64
+
+
+class Cf32(C.Structure):
+    """aeth_cf32 by value (aeth_seq_chips)"""
+    _fields_ = [("re", C.c_float), ("im", C.c_float)]
+
 
 # name -> (restype, argtypes); mirrors include/aether_hip.h declaration by declaration
 PROTOTYPES = {
@@ -143,6 +150,17 @@ PROTOTYPES = {
     "aeth_corr_exec": (i32, [vp, vp, vp, sz, vp]),
     "aeth_corr_exec_levels": (i32, [vp, vp, vp, sz, i32, vp, sz]),
     "aeth_corr_search": (i32, [vp, vp, vp, sz, vp, sz, vp]),
+    "aeth_seq_window": (i32, [vp, u64, u64, C.POINTER(u64)]),
+    "aeth_seq_create": (i32, [vp, vp, sz, pvp]),
+    "aeth_seq_destroy": (i32, [vp]),
+    "aeth_seq_nregs": (sz, [vp]),
+    "aeth_seq_order": (sz, [vp, sz]),
+    "aeth_seq_chunk": (sz, [vp]),
+    "aeth_seq_bits": (i32, [vp, vp, u64, vp, sz]),
+    "aeth_seq_scramble": (i32, [vp, vp, u64, vp, vp, sz]),
+    "aeth_seq_chips": (i32, [vp, vp, u64, Cf32, Cf32, vp, sz]),
+    "aeth_seq_spread": (i32, [vp, vp, u64, vp, sz, sz, vp, sz]),
+    "aeth_host_seq_bits": (i32, [vp, vp, u64, vp, sz]),
 }
 
 _lib = None

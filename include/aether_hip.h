@@ -49,6 +49,7 @@ typedef struct aeth_ctx aeth_ctx;       /* device + stream + staging buffers    
 typedef struct aeth_fft aeth_fft;       /* replaces Cfft (src/fft.rs:134-159)     */
 typedef struct aeth_fir aeth_fir;       /* gives Fir<T> (src/fir.rs:3-22) a body  */
 typedef struct aeth_corr aeth_corr;     /* streaming correlator: a matched filter with fused level / peak stores */
+typedef struct aeth_seq aeth_seq;       /* LFSR sequences: sequence::generate (src/sequence.rs:47-53) for linear generators */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -376,6 +377,53 @@ struct aeth_corr_peak { size_t index; float norm; unsigned n_nan; };
  * (AETH_E_UNSUPPORTED otherwise).  The call's internal records live in the context (released by aeth_ctx_trim). */
 AETH_API int aeth_corr_search(aeth_corr *corr, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
                               struct aeth_corr_peak *peaks_dev, size_t n_peaks, struct aeth_corr_peak *best_host);
+
+/* ---- LFSR sequences: src/sequence.rs:18-53 ------------------------------------------------------ */
+/* sequence::generate(init, generator, len) (src/sequence.rs:47-53) runs any closure serially; every generator the reference
+ * documents is a linear recurrence over GF(2) -- seq[n] = seq[n-d1] ^ seq[n-d2] ^ ... (the simple_sequence test, :61-68;
+ * the LTE TS 36.211 7.2 example of the doc comment, :34-46; m-sequences, Gold codes).  For that class position p is
+ * reached in O(log p) by powers of a 64 x 64 bit matrix, so the device generates any range [skip, skip + n) with every
+ * wave starting on its own, and the consumers -- bits, XOR into a bit stream, chips, sign-flip spreading -- are fused
+ * into the same pass: the sequence itself never touches memory.  All integer, all bit-exact.
+ *
+ * A register is a set of DISTINCT delays d_k in 1 .. 64; its order is max d_k.  `init` is a word whose bit i is seq[i]
+ * for i < order, as sequence::expand(seed, order) gives it (:18-21); higher bits are ignored.  For n >= order
+ * seq[n] = XOR_k seq[n - d_k]: sequence::generate(expand(init, order), |n, s| (sum s[n - d_k]) % 2, len).  Positions
+ * below `order` return the init bits themselves; an all-zero init is legal and gives zeros.  A sequence object holds
+ * 1 .. 4 registers and emits the XOR of their sequences at the same position (Gold codes: two).  skip is any uint64_t;
+ * skip + n must not overflow (AETH_E_ARG).  Not mirrored here (the bindings do): generate returning `init` unchanged
+ * when len <= init.len() (:48), and expand's shift overflow for len > 64 (:20). */
+struct aeth_seq_reg { const uint32_t *delays; size_t ndelays; };
+/* Host only -- no context, no device: the 64 sequence bits at [skip, skip + 64) of ONE register, bit i = seq[skip + i]. */
+AETH_API int aeth_seq_window(const struct aeth_seq_reg *reg, uint64_t init, uint64_t skip, uint64_t *window);
+/* Validates (null pointers; nregs outside 1 .. 4; ndelays outside 1 .. 64; a delay of 0 or above 64; repeated delays: all
+ * AETH_E_ARG) before any device work, then keeps the matrix powers and uploads the device jump table once. */
+AETH_API int aeth_seq_create(aeth_ctx *ctx, const struct aeth_seq_reg *regs, size_t nregs, aeth_seq **out);
+AETH_API int aeth_seq_destroy(aeth_seq *seq);
+AETH_API size_t aeth_seq_nregs(const aeth_seq *seq);
+AETH_API size_t aeth_seq_order(const aeth_seq *seq, size_t reg);
+AETH_API size_t aeth_seq_chunk(const aeth_seq *seq);   /* consecutive positions one wave generates from one jump-ahead */
+/* Device calls, stream-ordered like every other device call.  `init` points to nregs words on the HOST and is read
+ * before the call returns (the registers' windows at `skip` are computed on the host, in microseconds, and travel as
+ * kernel arguments).  With c[i] the sequence bit at position skip + i (generate's output, src/sequence.rs:47-53):
+ *   bits      out[i] = c[i], one byte per bit, values {0, 1}: the reference's Vec<u8> and aeth_modulate's input.
+ *   scramble  out[i] = (in[i] & 1) ^ c[i]; out == in is allowed, any other overlap is AETH_E_ARG.
+ *   chips     out[i] = c[i] ? one : zero, the two values copied bit for bit ((1,1) / (-1,-1): the reference's BPSK table,
+ *             src/modulation.rs:77).
+ *   spread    out[i] = sym[i / sf] with the sign bit of both components flipped where c[i] == 1: a multiplication by
+ *             +-1 that is exact for -0.0 and NaN payloads too.  n_out != nsym * sf -> AETH_E_LEN; sf >= 1; sf == 1 with
+ *             out == sym scrambles the symbols in place (twice: despreads), any other overlap is AETH_E_ARG.
+ * bits and scramble take any byte alignment; cf32 pointers are 8-byte aligned (AETH_E_ALIGN).  n == 0 -> AETH_OK without
+ * a launch.  At most 2^46 positions per call (AETH_E_UNSUPPORTED).  Everything is validated before any device work. */
+AETH_API int aeth_seq_bits(aeth_seq *seq, const uint64_t *init, uint64_t skip, uint8_t *bits_dev, size_t n);
+AETH_API int aeth_seq_scramble(aeth_seq *seq, const uint64_t *init, uint64_t skip, const uint8_t *in_dev, uint8_t *out_dev,
+                               size_t n);
+AETH_API int aeth_seq_chips(aeth_seq *seq, const uint64_t *init, uint64_t skip, aeth_cf32 zero, aeth_cf32 one,
+                            aeth_cf32 *out_dev, size_t n);
+AETH_API int aeth_seq_spread(aeth_seq *seq, const uint64_t *init, uint64_t skip, const aeth_cf32 *sym_dev, size_t nsym,
+                             size_t sf, aeth_cf32 *out_dev, size_t n_out);
+/* generate + download into a host slice; waits (sequence::generate's own shape, src/sequence.rs:47-53) */
+AETH_API int aeth_host_seq_bits(aeth_seq *seq, const uint64_t *init, uint64_t skip, uint8_t *bits_host, size_t n);
 
 /* ---- pinned host buffers: src/pool.rs:43-221 -------------------------------------------------- */
 /* The reference's object pool ("useful for large buffers and other time expensive objects", :9-10) with pinned

@@ -454,6 +454,77 @@ private:
     aeth_corr *h_ = nullptr;
 };
 
+// ---- sequence::expand / sequence::generate for linear generators (src/sequence.rs:18-53) ----------------------------
+// A register is the set of its delays: seq[n] = XOR seq[n - d]; 1 .. 4 registers XORed (Gold codes: two).  `init` holds
+// one word per register, bit i = seq[i] (what expand() unpacks).  Device pointers in and out; bits are one byte each.
+namespace sequence {
+inline std::vector<uint8_t> expand(uint64_t seed, size_t len)                       // :18-21 (len > 64 panics there)
+{
+    if (len > 64) throw Panic(AETH_E_ARG, "attempt to shift right with overflow");
+    std::vector<uint8_t> v(len);
+    for (size_t i = 0; i < len; i++) v[i] = (uint8_t)((seed >> i) & 1u);
+    return v;
+}
+// the 64 values at [skip, skip + 64) of one register, on the host
+inline uint64_t window(const std::vector<uint32_t> &delays, uint64_t init, uint64_t skip)
+{
+    aeth_seq_reg r{delays.data(), delays.size()};
+    uint64_t w = 0;
+    check(aeth_seq_window(&r, init, skip, &w));
+    return w;
+}
+}  // namespace sequence
+
+class Sequence {
+public:
+    Sequence(Context &ctx, const std::vector<std::vector<uint32_t>> &regs) : ctx_(&ctx)
+    {
+        std::vector<aeth_seq_reg> r;
+        for (const auto &d : regs) r.push_back(aeth_seq_reg{d.data(), d.size()});
+        check(aeth_seq_create(ctx.get(), r.data(), r.size(), &h_));
+    }
+    ~Sequence() { aeth_seq_destroy(h_); }
+    Sequence(const Sequence &) = delete;
+    Sequence &operator=(const Sequence &) = delete;
+    size_t nregs() const { return aeth_seq_nregs(h_); }
+    size_t order(size_t reg = 0) const { return aeth_seq_order(h_, reg); }
+    size_t chunk() const { return aeth_seq_chunk(h_); }
+    // c[i], i in [skip, skip + n), one byte per bit
+    void bits(const std::vector<uint64_t> &init, uint64_t skip, uint8_t *bits_dev, size_t n) { check(aeth_seq_bits(h_, words(init), skip, bits_dev, n)); }
+    // sequence::generate's own shape (:47-53): a host vector comes back
+    std::vector<uint8_t> generate(const std::vector<uint64_t> &init, size_t n, uint64_t skip = 0)
+    {
+        std::vector<uint8_t> v(n);
+        check(aeth_host_seq_bits(h_, words(init), skip, v.data(), n));
+        return v;
+    }
+    // out = (in & 1) ^ c; out == in runs in place
+    void scramble(const std::vector<uint64_t> &init, uint64_t skip, const uint8_t *in_dev, uint8_t *out_dev, size_t n)
+    {
+        check(aeth_seq_scramble(h_, words(init), skip, in_dev, out_dev, n));
+    }
+    // out = c ? one : zero (defaults: GENERIC_BPSK_TABLE, src/modulation.rs:77)
+    void chips(const std::vector<uint64_t> &init, uint64_t skip, DeviceVec &out, cf32 zero = {1.f, 1.f}, cf32 one = {-1.f, -1.f})
+    {
+        check(aeth_seq_chips(h_, words(init), skip, *raw(&zero), *raw(&one), out.ptr(), out.len()));
+    }
+    // out[i] = sym[i / sf], negated where c[i] == 1; sf == 1 with &out == &sym runs in place
+    void spread(const std::vector<uint64_t> &init, uint64_t skip, const DeviceVec &sym, size_t sf, DeviceVec &out)
+    {
+        check(aeth_seq_spread(h_, words(init), skip, sym.ptr(), sym.len(), sf, out.ptr(), out.len()));
+    }
+    aeth_seq *get() const { return h_; }
+
+private:
+    const uint64_t *words(const std::vector<uint64_t> &init) const
+    {
+        if (init.size() != nregs()) throw Panic(AETH_E_LEN, "one init word per register");
+        return init.data();
+    }
+    Context *ctx_;
+    aeth_seq *h_ = nullptr;
+};
+
 // ---- pipeline (src/pipeline.rs:24-41 add_stage, :123-137 new, :89-114 the per-stage report) ------------------
 // The reference chains closures over channels; the device pipeline has five fixed stages (copy-in | upload | compute |
 // download | copy-out) and the compute stage is one of the library's ops:

@@ -7,6 +7,7 @@ use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_fft { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_fir { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_corr { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_seq { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
 pub const AETH_POOL_ZERO_ON_RETURN: c_int = 1;
@@ -28,6 +29,10 @@ pub struct aeth_vec_stats_t { pub n: usize, pub n_nan: usize, pub min_index: usi
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct aeth_corr_peak { pub index: usize, pub norm: c_float, pub n_nan: c_uint }
+/// aeth_seq_reg: one register of a sequence object, seq[n] = XOR seq[n - delays[k]] (src/sequence.rs:42)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct aeth_seq_reg { pub delays: *const u32, pub ndelays: usize }
 pub const AETH_LEVEL_NORM: c_int = 0; pub const AETH_LEVEL_DB: c_int = 1; pub const AETH_LEVEL_POWER_DB: c_int = 2;
 /// aeth_stream_op: the compute stage of the host pipeline (src/pipeline.rs:24-41 takes a closure; a closure cannot
 /// cross the C ABI, so the stage is one of the library's device ops, described field by field as in aether_hip.h)
@@ -160,6 +165,19 @@ extern "C" {
                                  levels: *mut c_float, n_levels: usize) -> c_int;
     pub fn aeth_corr_search(corr: *mut aeth_corr, hist: *const cf32, inp: *const cf32, n: usize, peaks: *mut aeth_corr_peak,
                             n_peaks: usize, best: *mut aeth_corr_peak) -> c_int;
+    // sequence::generate for linear generators (src/sequence.rs:47-53): init = one word per register on the host
+    pub fn aeth_seq_window(reg: *const aeth_seq_reg, init: u64, skip: u64, window: *mut u64) -> c_int;
+    pub fn aeth_seq_create(ctx: *mut aeth_ctx, regs: *const aeth_seq_reg, nregs: usize, out: *mut *mut aeth_seq) -> c_int;
+    pub fn aeth_seq_destroy(seq: *mut aeth_seq) -> c_int;
+    pub fn aeth_seq_nregs(seq: *const aeth_seq) -> usize;
+    pub fn aeth_seq_order(seq: *const aeth_seq, reg: usize) -> usize;
+    pub fn aeth_seq_chunk(seq: *const aeth_seq) -> usize;
+    pub fn aeth_seq_bits(seq: *mut aeth_seq, init: *const u64, skip: u64, bits: *mut u8, n: usize) -> c_int;
+    pub fn aeth_seq_scramble(seq: *mut aeth_seq, init: *const u64, skip: u64, inp: *const u8, out: *mut u8, n: usize) -> c_int;
+    pub fn aeth_seq_chips(seq: *mut aeth_seq, init: *const u64, skip: u64, zero: cf32, one: cf32, out: *mut cf32, n: usize) -> c_int;
+    pub fn aeth_seq_spread(seq: *mut aeth_seq, init: *const u64, skip: u64, sym: *const cf32, nsym: usize, sf: usize,
+                           out: *mut cf32, n_out: usize) -> c_int;
+    pub fn aeth_host_seq_bits(seq: *mut aeth_seq, init: *const u64, skip: u64, bits: *mut u8, n: usize) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;
