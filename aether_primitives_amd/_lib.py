@@ -161,6 +161,18 @@ PROTOTYPES = {
     "aeth_seq_chips": (i32, [vp, vp, u64, Cf32, Cf32, vp, sz]),
     "aeth_seq_spread": (i32, [vp, vp, u64, vp, sz, sz, vp, sz]),
     "aeth_host_seq_bits": (i32, [vp, vp, u64, vp, sz]),
+    "aeth_chan_create": (i32, [vp, vp, sz, sz, sz, i32, sz, pvp]),
+    "aeth_chan_destroy": (i32, [vp]),
+    "aeth_chan_channels": (sz, [vp]),
+    "aeth_chan_ntaps": (sz, [vp]),
+    "aeth_chan_hop": (sz, [vp]),
+    "aeth_chan_phase": (i32, [vp]),
+    "aeth_chan_route": (C.c_char_p, [vp]),
+    "aeth_chan_tile": (sz, [vp]),
+    "aeth_chan_fold": (i32, [vp, vp, vp, sz, u64, vp, sz]),
+    "aeth_chan_exec": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, vp, sz]),
+    "aeth_chan_exec_levels": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, i32, i32, vp, sz]),
+    "aeth_chan_prototype": (i32, [i32, sz, sz, vp]),
 }
 
 _lib = None

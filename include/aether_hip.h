@@ -50,6 +50,7 @@ typedef struct aeth_fft aeth_fft;       /* replaces Cfft (src/fft.rs:134-159)   
 typedef struct aeth_fir aeth_fir;       /* gives Fir<T> (src/fir.rs:3-22) a body  */
 typedef struct aeth_corr aeth_corr;     /* streaming correlator: a matched filter with fused level / peak stores */
 typedef struct aeth_seq aeth_seq;       /* LFSR sequences: sequence::generate (src/sequence.rs:47-53) for linear generators */
+typedef struct aeth_chan aeth_chan;     /* polyphase analysis filter bank: windowed, overlapped frames in front of aeth_fft */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -424,6 +425,82 @@ AETH_API int aeth_seq_spread(aeth_seq *seq, const uint64_t *init, uint64_t skip,
                              size_t sf, aeth_cf32 *out_dev, size_t n_out);
 /* generate + download into a host slice; waits (sequence::generate's own shape, src/sequence.rs:47-53) */
 AETH_API int aeth_host_seq_bits(aeth_seq *seq, const uint64_t *init, uint64_t skip, uint8_t *bits_host, size_t n);
+
+/* ---- polyphase analysis filter bank (no body in the reference) --------------------------------- */
+/* The reference cuts a stream into frames with chunks_mut(fft_len) (`waterfall`, src/util/plot.rs:46-68, :59-61):
+ * disjoint, rectangular frames of exactly fft_len samples.  A receiver needs a window (so that a strong carrier does not
+ * leak over the whole waterfall), overlap between frames (Welch / STFT) and a prototype filter longer than the
+ * transform (the polyphase channelizer that splits a capture into M decimated channels).  All three are one operation:
+ * weight L = P * M samples, fold them modulo M, transform M points, advance by the hop D.
+ *   P = 1, D = M, w = 1   the reference's framing          P = 1, D < M   a windowed, overlapped spectrogram
+ *   P > 1, D = M          the critically sampled channelizer   P > 1, D < M   the oversampled one
+ * An aeth_chan is made of a REAL prototype w[0 .. L) (host floats, copied), channels = M, hop = D and a phase mode.
+ * L = ntaps is a multiple of M, P = L / M in 1 .. 64, D in 1 .. M.
+ *
+ * The stream: s[i] = in_dev[i] for 0 <= i < n; for -(L - D) <= i < 0 it is hist_dev[L - D + i], or zero when hist_dev
+ * is NULL (the FIR's convention; hist_dev is ignored when L == D).  n must be a multiple of D (AETH_E_LEN); the call
+ * makes F = n / D frames.  Frame m ends with the D newest samples: it covers s[(m + 1) * D - L + j], j = 0 .. L - 1, so
+ * the chunks of a stream concatenate exactly when the caller passes the previous L - D samples as history.
+ *
+ * The fold is defined bit for bit (f32, no contraction).  For q = 0 .. M - 1, with r = (q - rot) mod M:
+ *     u_m[q] = sum over p = 0 .. P - 1, ascending, of  w[p * M + r] * s[(m + 1) * D - L + p * M + r]
+ * every product rounded, the sum started from the p = 0 product (not from +0), products added left to right, re and im
+ * independently.
+ *   AETH_CHAN_PHASE_FRAME   rot = 0: the phase of every frame refers to its own first sample (STFT).
+ *   AETH_CHAN_PHASE_STREAM  rot = ((g + 1) * D) mod M with g = first_frame + m the global frame number (g + 1 is reduced
+ *                           modulo M before the multiplication: first_frame is any uint64_t).  Bin k is then the stream
+ *                           mixed by exp(sign * 2 pi i k t / M), t counted from the first sample ever fed, filtered by w
+ *                           and decimated by D: what an oversampled channelizer needs.  rot is 0 when D == M.
+ * The transform: X_m = Scale * DFT_M(u_m), sign and Scale as for aeth_fft_exec, through an aeth_fft plan the object owns.
+ *
+ * All exec calls are ordered on the context's in-order stream and validate everything before any device work: NULL
+ * pointers AETH_E_ARG; n == 0, n not a multiple of D, or an output count other than F * M AETH_E_LEN; cf32 pointers
+ * 8-byte and level pointers 4-byte aligned (AETH_E_ALIGN); the output range clear of the input and the history
+ * (AETH_E_ARG).  Element counts are size_t. */
+enum { AETH_CHAN_PHASE_FRAME = 0, AETH_CHAN_PHASE_STREAM = 1 };
+enum { AETH_CHAN_PROTO_RECT = 0, AETH_CHAN_PROTO_HANN = 1, AETH_CHAN_PROTO_HAMMING = 2, AETH_CHAN_PROTO_SINC_HAMMING = 3 };
+/* No body in the reference (its framing, src/util/plot.rs:46-68, is the P = 1, D = M, w = 1 case).  The inner plan is
+ * made by aeth_fft_create(ctx, channels, ...): a transform length it refuses fails here with its code and its message
+ * naming the length, and nothing stays allocated.  P > 64: AETH_E_UNSUPPORTED; any other violation of the rules above:
+ * AETH_E_ARG.  max_frames > 0 sizes the scratch of exec / exec_levels at creation; it grows on demand like the plan's. */
+AETH_API int aeth_chan_create(aeth_ctx *ctx, const float *proto_host, size_t ntaps, size_t channels, size_t hop, int phase,
+                              size_t max_frames, aeth_chan **out);
+/* No body in the reference (src/util/plot.rs:46-68 frames without an object).  Waits for the context's stream. */
+AETH_API int aeth_chan_destroy(aeth_chan *chan);
+/* No body in the reference (src/util/plot.rs:46-68: fft_len is an argument there): M, L, D and the phase mode. */
+AETH_API size_t aeth_chan_channels(const aeth_chan *chan);
+AETH_API size_t aeth_chan_ntaps(const aeth_chan *chan);
+AETH_API size_t aeth_chan_hop(const aeth_chan *chan);
+AETH_API int aeth_chan_phase(const aeth_chan *chan);
+/* No body in the reference (src/util/plot.rs:46-68 plans inside the call): the inner plan's aeth_fft_route text, owned
+ * by the object. */
+AETH_API const char *aeth_chan_route(const aeth_chan *chan);
+/* No body in the reference (src/util/plot.rs:46-68): consecutive frames one workgroup (hop == M with P <= 8: one lane)
+ * folds, like aeth_seq_chunk: the launch geometry, for tests that want to cross its edges. */
+AETH_API size_t aeth_chan_tile(const aeth_chan *chan);
+/* No body in the reference (src/util/plot.rs:46-68, chunks_mut(fft_len), is its w = 1, P = 1, D = M case): the front end
+ * alone, out_dev[m * M + q] = u_m[q], n_out == F * M.  16 B per output sample when every input comes from HBM once. */
+AETH_API int aeth_chan_fold(aeth_chan *chan, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
+                            uint64_t first_frame, aeth_cf32 *out_dev, size_t n_out);
+/* No body in the reference (src/util/plot.rs:46-68 runs vec_rfft on disjoint chunks): the fold into the object's
+ * scratch, then aeth_fft_exec of the F frames into out_dev; bit-identical to aeth_chan_fold followed by aeth_fft_exec. */
+AETH_API int aeth_chan_exec(aeth_chan *chan, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
+                            uint64_t first_frame, int sign, int scale_kind, float x, aeth_cf32 *out_dev, size_t n_out);
+/* No body in the reference (the whole `waterfall`, src/util/plot.rs:46-68, with a window and overlap): the fold into
+ * scratch, then aeth_fft_exec_levels; bit-identical to aeth_chan_fold followed by aeth_fft_exec_levels, so the
+ * register-resident power-of-two M never write the spectrum.  n_levels == F * M. */
+AETH_API int aeth_chan_exec_levels(aeth_chan *chan, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
+                                   uint64_t first_frame, int sign, int scale_kind, float x, int mirror, int level_kind,
+                                   float *levels_dev, size_t n_levels);
+/* No body in the reference (src/util/plot.rs:46-68 has no window).  Host only, needs no context: L = channels *
+ * taps_per_channel taps, computed in f64 and rounded once to f32, n = 0 .. L - 1:
+ *   RECT          1
+ *   HANN          0.5 - 0.5 cos(2 pi n / L)        (periodic)
+ *   HAMMING       0.54 - 0.46 cos(2 pi n / L)      (periodic)
+ *   SINC_HAMMING  the low-pass of cutoff fs / (2 M): sinc((n - (L - 1) / 2) / M) * (0.54 - 0.46 cos(2 pi n / (L - 1))),
+ *                 divided by its f64 sum (unit DC gain); L = 1 gives 1
+ * A bad kind or a zero size: AETH_E_ARG. */
+AETH_API int aeth_chan_prototype(int kind, size_t channels, size_t taps_per_channel, float *out_host);
 
 /* ---- pinned host buffers: src/pool.rs:43-221 -------------------------------------------------- */
 /* The reference's object pool ("useful for large buffers and other time expensive objects", :9-10) with pinned

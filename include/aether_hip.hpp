@@ -454,6 +454,57 @@ private:
     aeth_corr *h_ = nullptr;
 };
 
+// ---- polyphase analysis filter bank (no body in the reference: `waterfall`, src/util/plot.rs:46-68, frames with
+// chunks_mut(fft_len)) ---------------------------------------------------------------------------------------------------
+// Weight proto.size() = P * channels samples, fold them modulo `channels`, transform, advance by `hop`.
+class Channelizer {
+public:
+    Channelizer(Context &ctx, const std::vector<float> &proto, size_t channels, size_t hop = 0, int phase = AETH_CHAN_PHASE_FRAME,
+                size_t max_frames = 0)
+    {
+        check(aeth_chan_create(ctx.get(), proto.data(), proto.size(), channels, hop ? hop : channels, phase, max_frames, &h_));
+    }
+    ~Channelizer() { aeth_chan_destroy(h_); }
+    Channelizer(const Channelizer &) = delete;
+    Channelizer &operator=(const Channelizer &) = delete;
+    // RECT / HANN / HAMMING / SINC_HAMMING (AETH_CHAN_PROTO_*), computed on the host
+    static std::vector<float> prototype(int kind, size_t channels, size_t taps_per_channel)
+    {
+        std::vector<float> w(channels * taps_per_channel);
+        check(aeth_chan_prototype(kind, channels, taps_per_channel, w.data()));
+        return w;
+    }
+    size_t channels() const { return aeth_chan_channels(h_); }
+    size_t ntaps() const { return aeth_chan_ntaps(h_); }
+    size_t hop() const { return aeth_chan_hop(h_); }
+    int phase() const { return aeth_chan_phase(h_); }
+    size_t tile() const { return aeth_chan_tile(h_); }
+    std::string route() const { return aeth_chan_route(h_); }
+    size_t frames(size_t n) const { return n / hop(); }
+    // `hist`: the ntaps - hop samples in front of x (null: zeros); first_frame: the global number of the call's first frame
+    void fold(const DeviceVec &x, DeviceVec &out, const DeviceVec *hist = nullptr, uint64_t first_frame = 0)
+    {
+        check(aeth_chan_fold(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), first_frame, out.ptr(), out.len()));
+    }
+    void exec(const DeviceVec &x, DeviceVec &out, Scale s, const DeviceVec *hist = nullptr, uint64_t first_frame = 0,
+              int sign = AETH_SIGN_REF_FWD)
+    {
+        check(aeth_chan_exec(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), first_frame, sign, s.kind, s.x, out.ptr(), out.len()));
+    }
+    DeviceF32 levels(const DeviceVec &x, Scale s, bool mirror = false, int kind = AETH_LEVEL_NORM, const DeviceVec *hist = nullptr,
+                     uint64_t first_frame = 0, int sign = AETH_SIGN_REF_FWD)
+    {
+        DeviceF32 out(x.ctx(), frames(x.len()) * channels());
+        check(aeth_chan_exec_levels(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), first_frame, sign, s.kind, s.x, mirror ? 1 : 0,
+                                    kind, out.ptr(), out.len()));
+        return out;
+    }
+    aeth_chan *get() const { return h_; }
+
+private:
+    aeth_chan *h_ = nullptr;
+};
+
 // ---- sequence::expand / sequence::generate for linear generators (src/sequence.rs:18-53) ----------------------------
 // A register is the set of its delays: seq[n] = XOR seq[n - d]; 1 .. 4 registers XORed (Gold codes: two).  `init` holds
 // one word per register, bit i = seq[i] (what expand() unpacks).  Device pointers in and out; bits are one byte each.

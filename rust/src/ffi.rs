@@ -8,6 +8,7 @@ use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_fir { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_corr { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_seq { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_chan { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
 pub const AETH_POOL_ZERO_ON_RETURN: c_int = 1;
@@ -33,6 +34,9 @@ pub struct aeth_corr_peak { pub index: usize, pub norm: c_float, pub n_nan: c_ui
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct aeth_seq_reg { pub delays: *const u32, pub ndelays: usize }
+pub const AETH_CHAN_PHASE_FRAME: c_int = 0; pub const AETH_CHAN_PHASE_STREAM: c_int = 1;
+pub const AETH_CHAN_PROTO_RECT: c_int = 0; pub const AETH_CHAN_PROTO_HANN: c_int = 1; pub const AETH_CHAN_PROTO_HAMMING: c_int = 2;
+pub const AETH_CHAN_PROTO_SINC_HAMMING: c_int = 3;
 pub const AETH_LEVEL_NORM: c_int = 0; pub const AETH_LEVEL_DB: c_int = 1; pub const AETH_LEVEL_POWER_DB: c_int = 2;
 /// aeth_stream_op: the compute stage of the host pipeline (src/pipeline.rs:24-41 takes a closure; a closure cannot
 /// cross the C ABI, so the stage is one of the library's device ops, described field by field as in aether_hip.h)
@@ -178,6 +182,23 @@ extern "C" {
     pub fn aeth_seq_spread(seq: *mut aeth_seq, init: *const u64, skip: u64, sym: *const cf32, nsym: usize, sf: usize,
                            out: *mut cf32, n_out: usize) -> c_int;
     pub fn aeth_host_seq_bits(seq: *mut aeth_seq, init: *const u64, skip: u64, bits: *mut u8, n: usize) -> c_int;
+    pub fn aeth_chan_create(ctx: *mut aeth_ctx, proto_host: *const c_float, ntaps: usize, channels: usize, hop: usize, phase: c_int,
+                            max_frames: usize, out: *mut *mut aeth_chan) -> c_int;
+    pub fn aeth_chan_destroy(chan: *mut aeth_chan) -> c_int;
+    pub fn aeth_chan_channels(chan: *const aeth_chan) -> usize;
+    pub fn aeth_chan_ntaps(chan: *const aeth_chan) -> usize;
+    pub fn aeth_chan_hop(chan: *const aeth_chan) -> usize;
+    pub fn aeth_chan_phase(chan: *const aeth_chan) -> c_int;
+    pub fn aeth_chan_route(chan: *const aeth_chan) -> *const c_char;
+    pub fn aeth_chan_tile(chan: *const aeth_chan) -> usize;
+    pub fn aeth_chan_fold(chan: *mut aeth_chan, hist_dev: *const cf32, in_dev: *const cf32, n: usize, first_frame: u64,
+                          out_dev: *mut cf32, n_out: usize) -> c_int;
+    pub fn aeth_chan_exec(chan: *mut aeth_chan, hist_dev: *const cf32, in_dev: *const cf32, n: usize, first_frame: u64, sign: c_int,
+                          scale_kind: c_int, x: c_float, out_dev: *mut cf32, n_out: usize) -> c_int;
+    pub fn aeth_chan_exec_levels(chan: *mut aeth_chan, hist_dev: *const cf32, in_dev: *const cf32, n: usize, first_frame: u64,
+                                 sign: c_int, scale_kind: c_int, x: c_float, mirror: c_int, level_kind: c_int,
+                                 levels_dev: *mut c_float, n_levels: usize) -> c_int;
+    pub fn aeth_chan_prototype(kind: c_int, channels: usize, taps_per_channel: usize, out_host: *mut c_float) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;

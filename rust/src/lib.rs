@@ -269,6 +269,39 @@ impl<'c> Fir<'c> {
 }
 impl<'c> Drop for Fir<'c> { fn drop(&mut self) { unsafe { aeth_fir_destroy(self.h); } } }
 
+/// Polyphase analysis filter bank (no body in the reference: `waterfall`, src/util/plot.rs:46-68, frames with
+/// chunks_mut(fft_len)): weight `proto.len()` = P * channels samples, fold them modulo `channels`, transform, advance by
+/// `hop`.  `stream_phase`: bin phases refer to the first sample ever fed (pass the global number of a call's first frame).
+pub struct Channelizer<'c> { h: *mut aeth_chan, _ctx: PhantomData<&'c Context> }
+impl<'c> Channelizer<'c> {
+    pub fn new(ctx: &'c Context, proto: &[f32], channels: usize, hop: usize, stream_phase: bool) -> Channelizer<'c> {
+        let mut h = ptr::null_mut();
+        let phase = if stream_phase { AETH_CHAN_PHASE_STREAM } else { AETH_CHAN_PHASE_FRAME };
+        check(unsafe { aeth_chan_create(ctx.h, proto.as_ptr(), proto.len(), channels, hop, phase, 0, &mut h) });
+        Channelizer { h, _ctx: PhantomData }
+    }
+    /// RECT / HANN / HAMMING / SINC_HAMMING taps (AETH_CHAN_PROTO_*), computed on the host
+    pub fn prototype(kind: i32, channels: usize, taps_per_channel: usize) -> Vec<f32> {
+        let mut w = vec![0f32; channels * taps_per_channel];
+        check(unsafe { aeth_chan_prototype(kind, channels, taps_per_channel, w.as_mut_ptr()) });
+        w
+    }
+    pub fn channels(&self) -> usize { unsafe { aeth_chan_channels(self.h) } }
+    pub fn hop(&self) -> usize { unsafe { aeth_chan_hop(self.h) } }
+    pub fn frames(&self, n: usize) -> usize { n / self.hop() }
+    /// the folded frames alone; `hist`: the ntaps - hop samples in front of x (None: zeros)
+    pub fn fold(&mut self, x: &DeviceVec, hist: Option<&DeviceVec>, first_frame: u64, out: &mut DeviceVec) {
+        check(unsafe { aeth_chan_fold(self.h, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n, first_frame, out.p, out.n) });
+    }
+    /// fold, then `fwd` with Scale `s` on every frame
+    pub fn exec(&mut self, x: &DeviceVec, hist: Option<&DeviceVec>, first_frame: u64, s: Scale, out: &mut DeviceVec) {
+        let (kind, xs) = scale_args(s);
+        check(unsafe { aeth_chan_exec(self.h, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n, first_frame,
+                                      AETH_SIGN_REF_FWD, kind, xs, out.p, out.n) });
+    }
+}
+impl<'c> Drop for Channelizer<'c> { fn drop(&mut self) { unsafe { aeth_chan_destroy(self.h); } } }
+
 /// The device counterpart of `pipeline::new().add_stage(..)` (src/pipeline.rs:24-41, :123-137): five fixed stages --
 /// copy-in | upload | compute | download | copy-out -- whose compute stage is one of the library's device ops (a closure
 /// cannot cross the C ABI).  `run` takes host slices and returns what `aeth_stream_host` reports.
