@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <memory>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 using namespace aeth::fftk;
@@ -35,6 +36,20 @@ using namespace aeth::fftk;
 using namespace aeth::firk;
 
 namespace {
+
+// the fused kernel has store variants (demodulating, decimating, level, peak) for these lengths, one block per workgroup
+constexpr bool fused_store_len(size_t n) { return 1024 <= n && n <= 4096; }
+
+// The one place a build of fmi_kernel is launched: the streaming (non-temporal) or the cached build by `nt`, then the
+// launch's status.  ONLY_NT: the variant ships as a streaming build alone and the caller has decided for it.
+template <class C, bool SCALED, int MINW, bool CHIRP, int VAR, bool ONLY_NT = false>
+int fmi_go(bool nt, int grid, hipStream_t stream, const FmiArgs &b)
+{
+    if (ONLY_NT || nt) hipLaunchKernelGGL((fmi_kernel<C, SCALED, MINW, true, CHIRP, VAR>), dim3(grid), dim3(C::WG), 0, stream, b);
+    else if constexpr (!ONLY_NT) hipLaunchKernelGGL((fmi_kernel<C, SCALED, MINW, false, CHIRP, VAR>), dim3(grid), dim3(C::WG), 0, stream, b);
+    AETH_HIP(hipGetLastError());
+    return AETH_OK;
+}
 
 template <class C, bool SCALED>
 int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
@@ -64,12 +79,7 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
     if (b.frame_n == 0) b.frame_n = C::N;
     const bool nt = aeth::streams_past_cache(2 * (size_t)a.n * sizeof(float2));
     if constexpr (SCALED) {
-        if (b.chirp) {                                      // chirp-z frames always carry a scale factor
-            if (nt) hipLaunchKernelGGL((fmi_kernel<C, true, 1, true, true>), dim3(grid), dim3(C::WG), 0, stream, b);
-            else hipLaunchKernelGGL((fmi_kernel<C, true, 1, false, true>), dim3(grid), dim3(C::WG), 0, stream, b);
-            AETH_HIP(hipGetLastError());
-            return AETH_OK;
-        }
+        if (b.chirp) return fmi_go<C, true, 1, true, 0>(nt, grid, stream, b);   // chirp-z frames always carry a scale factor
     }
     // one-frame workgroups run their LDS exchanges at raised wave priority (V_PRIO: -0.3 ... -0.5 us per 16 Mi-sample
     // launch in tools/fir_lab, A/B in one process); the other variants of aeth_fir_kernel.h measured null or negative
@@ -78,7 +88,7 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
     constexpr int VAR = (C::F == 1) ? (V_PRIO | ((C::N == 2048 && C::P == 16) ? V_XOR : 0)) : 0;
     // the demodulating and decimating stores are built for the lengths the host routes to them, 1024 ... 4096
     // (aeth_fft_mul_ifft_demod, aeth_fir_exec_decim); no other length carries a build of either
-    constexpr bool kStoreVariants = C::F == 1 && 1024 <= C::N && C::N <= 4096;
+    constexpr bool kStoreVariants = C::F == 1 && fused_store_len(C::N);
     if constexpr (!kStoreVariants) {
         if (b.bits || b.dec.d > 1)
             return aeth::set_error(AETH_E_UNSUPPORTED, "fused FFT*H*IFFT: no demodulating / decimating build of length %d", C::N);
@@ -87,20 +97,16 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
         if (b.bits) {                                       // hard demodulation instead of the sample store
             // the decision's mode is a template parameter (aeth_fir_kernel.h: demod_block): BPSK, QPSK with a
             // separable table, QPSK with any other table -- nothing about it is tested per sample
-#define AETH_DM(DMV)                                                                                                                \
-            do {                                                                                                                    \
-                if constexpr (kLab8) {                                                                                              \
-                    if (lab8_four) { hipLaunchKernelGGL((fmi_kernel<C, SCALED, 4, true, false, VAR | V_DEMOD | (DMV)>), dim3(grid), dim3(C::WG), 0, stream, b); break; } \
-                }                                                                                                                   \
-                if (nt) hipLaunchKernelGGL((fmi_kernel<C, SCALED, 1, true, false, VAR | V_DEMOD | (DMV)>), dim3(grid), dim3(C::WG), 0, stream, b); \
-                else hipLaunchKernelGGL((fmi_kernel<C, SCALED, 1, false, false, VAR | V_DEMOD | (DMV)>), dim3(grid), dim3(C::WG), 0, stream, b);   \
-            } while (0)
-            if (b.bps == 1) AETH_DM(V_DM_BPSK);
-            else if (b.demod_sep) AETH_DM(0);
-            else AETH_DM(V_DM_QGEN);
-#undef AETH_DM
-            AETH_HIP(hipGetLastError());
-            return AETH_OK;
+            auto demod = [&](auto dmv) {
+                constexpr int DV = VAR | V_DEMOD | decltype(dmv)::value;
+                if constexpr (kLab8) {
+                    if (lab8_four) return fmi_go<C, SCALED, 4, false, DV, true>(nt, grid, stream, b);
+                }
+                return fmi_go<C, SCALED, 1, false, DV>(nt, grid, stream, b);
+            };
+            if (b.bps == 1) return demod(std::integral_constant<int, V_DM_BPSK>());
+            if (b.demod_sep) return demod(std::integral_constant<int, 0>());
+            return demod(std::integral_constant<int, V_DM_QGEN>());
         }
     }
     if constexpr (kStoreVariants && !SCALED) {
@@ -108,10 +114,7 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
             // without the swizzle: with it the N = 2048 build needs 260 VGPRs and drops to one wave per SIMD (62 us
             // per 16 Mi-sample launch against 50)
             constexpr int DV = (VAR & ~V_XOR) | V_DECIM;
-            if (nt) hipLaunchKernelGGL((fmi_kernel<C, false, 2, true, false, DV>), dim3(grid), dim3(C::WG), 0, stream, b);
-            else hipLaunchKernelGGL((fmi_kernel<C, false, 2, false, false, DV>), dim3(grid), dim3(C::WG), 0, stream, b);
-            AETH_HIP(hipGetLastError());
-            return AETH_OK;
+            return fmi_go<C, false, 2, false, DV>(nt, grid, stream, b);
         }
     }
     if constexpr (!(kStoreVariants && !SCALED)) {
@@ -125,19 +128,10 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
             // the transform of the plain build, swizzle included: the epilogues' own registers (f64 q, the logarithm of
             // the dB kinds) still fit -- N = 2048: 250 VGPRs for the peak and the norm, 255 for the dB kinds -- and
             // MINW = 2 holds every build to 256 (tests/test_corr_resources.py checks that none of them spills for it)
-            constexpr int CV = VAR;
-#define AETH_CORR(EXTRA)                                                                                                            \
-            do {                                                                                                                    \
-                if (cnt) hipLaunchKernelGGL((fmi_kernel<C, false, 2, true, false, CV | (EXTRA)>), dim3(grid), dim3(C::WG), 0, stream, b); \
-                else hipLaunchKernelGGL((fmi_kernel<C, false, 2, false, false, CV | (EXTRA)>), dim3(grid), dim3(C::WG), 0, stream, b);    \
-            } while (0)
-            if (b.parts) AETH_CORR(V_PEAK);
-            else if (b.level_kind == AETH_LEVEL_NORM) AETH_CORR(V_LEVEL);
-            else if (b.level_kind == AETH_LEVEL_DB) AETH_CORR(V_LEVEL | V_LV_DB);
-            else AETH_CORR(V_LEVEL | V_LV_POWER_DB);
-#undef AETH_CORR
-            AETH_HIP(hipGetLastError());
-            return AETH_OK;
+            if (b.parts) return fmi_go<C, false, 2, false, VAR | V_PEAK>(cnt, grid, stream, b);
+            if (b.level_kind == AETH_LEVEL_NORM) return fmi_go<C, false, 2, false, VAR | V_LEVEL>(cnt, grid, stream, b);
+            if (b.level_kind == AETH_LEVEL_DB) return fmi_go<C, false, 2, false, VAR | V_LEVEL | V_LV_DB>(cnt, grid, stream, b);
+            return fmi_go<C, false, 2, false, VAR | V_LEVEL | V_LV_POWER_DB>(cnt, grid, stream, b);
         }
     }
     // A launch that runs on its own (one queue, or the head of a chain) issues the next window's loads in four
@@ -147,16 +141,9 @@ int launch_fmi(aeth_ctx *ctx, const FmiArgs &a, hipStream_t stream)
     if constexpr (C::F == 1 && !SCALED && C::NPASS == 3) {
         const int sp = aeth::tuning_int("AETH_FIR_SPREAD", -1);
         const bool chained = ctx->overlap && !ctx->stream_shared && ctx->last_chained;
-        if (nt && (sp < 0 ? !chained : sp != 0)) {
-            hipLaunchKernelGGL((fmi_kernel<C, false, 1, true, false, VAR | V_SPREAD>), dim3(grid), dim3(C::WG), 0, stream, b);
-            AETH_HIP(hipGetLastError());
-            return AETH_OK;
-        }
+        if (nt && (sp < 0 ? !chained : sp != 0)) return fmi_go<C, false, 1, false, VAR | V_SPREAD, true>(nt, grid, stream, b);
     }
-    if (nt) hipLaunchKernelGGL((fmi_kernel<C, SCALED, 1, true, false, VAR>), dim3(grid), dim3(C::WG), 0, stream, b);
-    else hipLaunchKernelGGL((fmi_kernel<C, SCALED, 1, false, false, VAR>), dim3(grid), dim3(C::WG), 0, stream, b);
-    AETH_HIP(hipGetLastError());
-    return AETH_OK;
+    return fmi_go<C, SCALED, 1, false, VAR>(nt, grid, stream, b);
 }
 
 int dispatch_fmi(aeth_ctx *ctx, size_t fft_len, const FmiArgs &a, hipStream_t stream = nullptr)
@@ -184,12 +171,17 @@ int dispatch_fmi(aeth_ctx *ctx, size_t fft_len, const FmiArgs &a, hipStream_t st
 
 bool is_pow2(size_t n) { return n && (n & (n - 1)) == 0; }
 
-// [a, a + na) and [b, b + nb) share a byte?  (elements of 8 bytes)
-bool touch(const aeth_cf32 *a, size_t na, const aeth_cf32 *b, size_t nb)
+// [a, a + na) and [b, b + nb) share a byte?
+bool touch_bytes(const void *a, size_t na, const void *b, size_t nb)
 {
     if (!a || !b || !na || !nb) return false;
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na * sizeof(aeth_cf32), b0 = (uintptr_t)b, b1 = b0 + nb * sizeof(aeth_cf32);
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
     return a0 < b1 && b0 < a1;
+}
+// the same in samples
+bool touch(const aeth_cf32 *a, size_t na, const aeth_cf32 *b, size_t nb)
+{
+    return touch_bytes(a, na * sizeof(aeth_cf32), b, nb * sizeof(aeth_cf32));
 }
 
 // ---- aeth_corr_search: from the waves' records to the per-block records and the best of the stream -------------------
@@ -272,36 +264,25 @@ __global__ __launch_bounds__(kFoldBlock) void corr_best_kernel(const PeakBest *_
     if (threadIdx.x == 0) peak_record(out, q, idx, nnan, n);
 }
 
-int corr_slab_ensure(aeth_ctx *ctx, size_t bytes)
-{
-    if (ctx->corr_slab_bytes >= bytes) return AETH_OK;
-    if (ctx->corr_slab) {
-        AETH_HIP(hipStreamSynchronize(aeth::ctx_stream(ctx)));
-        AETH_HIP(hipFree(ctx->corr_slab));
-        ctx->corr_slab = nullptr; ctx->corr_slab_bytes = 0;
-    }
-    const size_t want = bytes + bytes / 4;
-    AETH_HIP(hipMalloc(&ctx->corr_slab, want));
-    ctx->corr_slab_bytes = want;
-    return AETH_OK;
-}
-
-// [a, a + na) and [b, b + nb) share a byte?
-bool touch_bytes(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
-}
-
 const char kMsgFirInPlace[] = "FIR cannot run in place: the output range overlaps the input (or its history)";
 const char kMsgFirAlign[] = "pointer not 8-byte aligned";
 
-// the arguments every correlator product hands to the fused kernel (those of aeth_fir_exec)
-FmiArgs corr_args(const aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n)
+// what aeth_fir_exec, aeth_fir_exec_decim and aeth_corr_exec ask of their buffers (`out` holds n_out samples)
+int fir_check(const aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, const aeth_cf32 *out, size_t n_out)
+{
+    AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
+    // blocks run concurrently and their windows reach into the neighbours' outputs: ANY overlap of the output range
+    // with the input or the history reads samples that were already overwritten (out = in + 100 as much as out = in)
+    AETH_REQUIRE(!touch(out, n_out, in, n) && !touch(out, n_out, hist, f->ntaps - 1), AETH_E_ARG, "%s", kMsgFirInPlace);
+    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(out) && aeth::aligned8(hist), AETH_E_ALIGN, "%s", kMsgFirAlign);
+    return AETH_OK;
+}
+
+// overlap-save over a stream of n samples; the products add their own fields (dec / n_out, levels, parts)
+FmiArgs fir_args(const aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, aeth_cf32 *out)
 {
     FmiArgs a;
-    a.in = (const cf *)in; a.out = nullptr; a.hist = (const cf *)hist; a.Hf = (const cf *)f->Hf;
+    a.in = (const cf *)in; a.out = (cf *)out; a.hist = (const cf *)hist; a.Hf = (const cf *)f->Hf;
     a.twN = (const cf *)f->fft->tw_dev; a.twL = (const cf *)f->fft->tw_lane_dev;
     a.n = (long long)n; a.hop = (int)f->hop; a.ov = (int)(f->fft_len - f->hop); a.nhist = (int)(f->ntaps - 1);
     a.nblocks = (long long)((n + f->hop - 1) / f->hop);
@@ -309,30 +290,37 @@ FmiArgs corr_args(const aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in,
     return a;
 }
 
+// `batch` frames of the plan's length, each a block of its own (no overlap, no history)
+FmiArgs frame_args(const aeth_fft *plan, const void *in, void *out, const void *Hf, size_t n_total, size_t batch, float s_fwd,
+                   float s_bwd)
+{
+    FmiArgs a;
+    a.in = (const cf *)in; a.out = (cf *)out; a.hist = nullptr; a.Hf = (const cf *)Hf;
+    a.twN = (const cf *)plan->tw_dev; a.twL = (const cf *)plan->tw_lane_dev;
+    a.n = (long long)n_total; a.nblocks = (long long)batch;
+    a.hop = (int)plan->len; a.ov = 0; a.nhist = 0;
+    a.s_fwd = s_fwd; a.s_bwd = s_bwd;
+    return a;
+}
+
 }  // namespace
 
 namespace aeth {
-
-void corr_slab_release(aeth_ctx *ctx)
-{
-    if (ctx->corr_slab) (void)hipFree(ctx->corr_slab);
-    ctx->corr_slab = nullptr;
-    ctx->corr_slab_bytes = 0;
-}
 
 // Chirp-z transform of `batch` frames of n samples in ONE launch: x*chirp -> fwd_M -> *filt -> bwd_M -> *chirp,
 // zero-padded to M = sub->len in registers (aeth_fft_big.hip: fft_run_bluestein, M <= 4096).
 int fmi_bluestein(aeth_fft *sub, const float2 *in, float2 *out, size_t n, size_t batch, const float2 *chirp,
                   const float2 *filt, int conj, float scale)
 {
-    FmiArgs a;
-    a.in = (const cf *)in; a.out = (cf *)out; a.hist = nullptr; a.Hf = (const cf *)filt;
-    a.twN = (const cf *)sub->tw_dev; a.twL = (const cf *)sub->tw_lane_dev;
-    a.n = (long long)(n * batch); a.nblocks = (long long)batch;
-    a.hop = (int)n; a.ov = 0; a.nhist = 0;
-    a.s_fwd = 1.0f; a.s_bwd = scale;
+    FmiArgs a = frame_args(sub, in, out, filt, n * batch, batch, 1.0f, scale);
+    a.hop = (int)n;                                          // frames of n samples, zero-padded to the plan's length
     a.chirp = (const cf *)chirp; a.frame_n = (int)n; a.conj = conj;
     return dispatch_fmi(sub->ctx, sub->len, a);
+}
+
+int fir_exec_on(aeth_fir *f, hipStream_t stream, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, aeth_cf32 *out)
+{
+    return dispatch_fmi(f->ctx, f->fft_len, fir_args(f, hist, in, n, out), stream);
 }
 
 }  // namespace aeth
@@ -349,7 +337,7 @@ int aeth_fft_mul_ifft(aeth_fft *plan, aeth_cf32 *frames, size_t n_total, size_t 
     AETH_REQUIRE(kind_fwd >= 0 && kind_fwd <= 3 && kind_bwd >= 0 && kind_bwd <= 3, AETH_E_ARG, "bad scale kind");
     if (batch == 0) return AETH_OK;
     AETH_REQUIRE(frames && sig, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(aeth::aligned8(frames) && aeth::aligned8(sig), AETH_E_ALIGN, "pointer not 8-byte aligned");
+    AETH_REQUIRE(aeth::aligned8(frames) && aeth::aligned8(sig), AETH_E_ALIGN, "%s", kMsgFirAlign);
     if (plan->algo != aeth::FFT_ALGO_POW2 || plan->len > 4096) {
         // generic lengths (and the 8192-point frame, too wide for the fused kernel's registers): the three trait calls, unfused
         int rc = aeth_fft_exec(plan, frames, n_total, frames, batch, AETH_SIGN_REF_FWD, kind_fwd, x_fwd);
@@ -358,13 +346,9 @@ int aeth_fft_mul_ifft(aeth_fft *plan, aeth_cf32 *frames, size_t n_total, size_t 
         if (rc) return rc;
         return aeth_fft_exec(plan, frames, n_total, frames, batch, AETH_SIGN_REF_BWD, kind_bwd, x_bwd);
     }
-    FmiArgs a;
-    a.in = (const cf *)frames; a.out = (cf *)frames; a.hist = nullptr; a.Hf = (const cf *)sig;
-    a.twN = (const cf *)plan->tw_dev; a.twL = (const cf *)plan->tw_lane_dev; a.n = (long long)n_total; a.nblocks = (long long)batch;
-    a.hop = (int)plan->len; a.ov = 0; a.nhist = 0;
-    a.s_fwd = aeth_scale_factor(kind_fwd, plan->len, x_fwd);
-    a.s_bwd = aeth_scale_factor(kind_bwd, plan->len, x_bwd);
-    return dispatch_fmi(plan->ctx, plan->len, a);
+    return dispatch_fmi(plan->ctx, plan->len,
+                        frame_args(plan, frames, frames, sig, n_total, batch, aeth_scale_factor(kind_fwd, plan->len, x_fwd),
+                                   aeth_scale_factor(kind_bwd, plan->len, x_bwd)));
 }
 
 /* frames.vec_rfft(fft, s).vec_mul(&sig).vec_rifft(fft, s) per frame (benches/benches.rs:410-416), then
@@ -387,7 +371,7 @@ int aeth_fft_mul_ifft_demod(aeth_fft *plan, const aeth_cf32 *frames, size_t n_to
     static const aeth_cf32 kB[2] = {{1.f, 1.f}, {-1.f, -1.f}};                              /* modulation.rs:77 */
     static const aeth_cf32 kQ[4] = {{1.f, 1.f}, {-1.f, 1.f}, {1.f, -1.f}, {-1.f, -1.f}};    /* modulation.rs:87-92 */
     const aeth_cf32 *tb = table ? table : (bps == 1 ? kB : kQ);
-    if (plan->algo != aeth::FFT_ALGO_POW2 || plan->len < 1024 || plan->len > 4096) {
+    if (plan->algo != aeth::FFT_ALGO_POW2 || !fused_store_len(plan->len)) {
         // other lengths: the chain on a copy in the plan's temp, then the stand-alone demodulator
         int rc = aeth::fft_ensure_tmp(plan, n_total); if (rc) return rc;
         rc = aeth_copy_dev(plan->ctx, plan->tmp_dev, frames, n_total * sizeof(float2)); if (rc) return rc;
@@ -395,12 +379,8 @@ int aeth_fft_mul_ifft_demod(aeth_fft *plan, const aeth_cf32 *frames, size_t n_to
         if (rc) return rc;
         return aeth_demod_naive(plan->ctx, (const aeth_cf32 *)plan->tmp_dev, n_total, bps, table, bits_out, nbits_out, compat);
     }
-    FmiArgs a;
-    a.in = (const cf *)frames; a.out = nullptr; a.hist = nullptr; a.Hf = (const cf *)sig;
-    a.twN = (const cf *)plan->tw_dev; a.twL = (const cf *)plan->tw_lane_dev; a.n = (long long)n_total; a.nblocks = (long long)batch;
-    a.hop = (int)plan->len; a.ov = 0; a.nhist = 0;
-    a.s_fwd = aeth_scale_factor(kind_fwd, plan->len, x_fwd);
-    a.s_bwd = aeth_scale_factor(kind_bwd, plan->len, x_bwd);
+    FmiArgs a = frame_args(plan, frames, nullptr, sig, n_total, batch, aeth_scale_factor(kind_fwd, plan->len, x_fwd),
+                           aeth_scale_factor(kind_bwd, plan->len, x_bwd));
     a.bits = bits_out; a.bps = bps; a.demod_compat = compat;
     for (int i = 0; i < (bps == 1 ? 2 : 4); i++) { cf t = {tb[i].re, tb[i].im}; a.tab[i] = t; }
     // demod_naive scans 2 * bps candidates (modulation.rs:135): all four for QPSK
@@ -473,21 +453,12 @@ int aeth_fir_exec(aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, size_
 {
     AETH_REQUIRE(f, AETH_E_ARG, "fir is null");
     if (n == 0) return AETH_OK;
-    AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
-    // blocks run concurrently and their windows reach into the neighbours' outputs: ANY overlap of the output range
-    // with the input or the history reads samples that were already overwritten (out = in + 100 as much as out = in)
-    AETH_REQUIRE(!touch(out, n, in, n) && !touch(out, n, hist, f->ntaps - 1), AETH_E_ARG, "%s", kMsgFirInPlace);
-    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(out) && aeth::aligned8(hist), AETH_E_ALIGN, "%s", kMsgFirAlign);
-    FmiArgs a;
-    a.in = (const cf *)in; a.out = (cf *)out; a.hist = (const cf *)hist; a.Hf = (const cf *)f->Hf; a.twN = (const cf *)f->fft->tw_dev; a.twL = (const cf *)f->fft->tw_lane_dev;
-    a.n = (long long)n; a.hop = (int)f->hop; a.ov = (int)(f->fft_len - f->hop); a.nhist = (int)(f->ntaps - 1);
-    a.nblocks = (long long)((n + f->hop - 1) / f->hop);
-    a.s_fwd = 1.0f; a.s_bwd = 1.0f;
+    if (int rc = fir_check(f, hist, in, n, out, n)) return rc;
     // independent consecutive launches alternate between the context's two queues (aeth_ctx_set_overlap); a history
     // buffer is usually the tail of something just written, so such calls stay on the in-order stream
     hipStream_t lane = hist ? aeth::ctx_stream(f->ctx)
                             : aeth::ctx_fir_lane(f->ctx, (uintptr_t)in, (uintptr_t)(in + n), (uintptr_t)out, (uintptr_t)(out + n));
-    return dispatch_fmi(f->ctx, f->fft_len, a, lane);
+    return aeth::fir_exec_on(f, lane, hist, in, n, out);
 }
 
 /* fir, then sampling::downsample(&y, &mut dst) (src/sampling.rs:28-42) in one pass: out[i] = y[i * dec],
@@ -500,42 +471,14 @@ int aeth_fir_exec_decim(aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in,
     AETH_REQUIRE(n >= n_out, AETH_E_LEN, "downsample from an empty src (the reference panics: index out of bounds)");
     const size_t dec = n / n_out;
     if (dec == 1) return aeth_fir_exec(f, hist, in, n, out);
-    AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!touch(out, n_out, in, n) && !touch(out, n_out, hist, f->ntaps - 1), AETH_E_ARG,
-                 "FIR cannot run in place: the output range overlaps the input (or its history)");
-    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(out) && aeth::aligned8(hist), AETH_E_ALIGN,
-                 "pointer not 8-byte aligned");
-    AETH_REQUIRE(f->fft_len >= 1024 && f->fft_len <= 4096, AETH_E_UNSUPPORTED,
+    if (int rc = fir_check(f, hist, in, n, out, n_out)) return rc;
+    AETH_REQUIRE(fused_store_len(f->fft_len), AETH_E_UNSUPPORTED,
                  "decimating store: fft_len %zu (one-block-per-workgroup lengths 1024 .. 4096 only)", f->fft_len);
     AETH_REQUIRE(n < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "decimating store: %zu samples (32-bit index arithmetic)", n);
-    FmiArgs a;
-    a.in = (const cf *)in; a.out = (cf *)out; a.hist = (const cf *)hist; a.Hf = (const cf *)f->Hf;
-    a.twN = (const cf *)f->fft->tw_dev; a.twL = (const cf *)f->fft->tw_lane_dev;
-    a.n = (long long)n; a.hop = (int)f->hop; a.ov = (int)(f->fft_len - f->hop); a.nhist = (int)(f->ntaps - 1);
-    a.nblocks = (long long)((n + f->hop - 1) / f->hop);
-    a.s_fwd = 1.0f; a.s_bwd = 1.0f;
+    FmiArgs a = fir_args(f, hist, in, n, out);
     a.dec = aeth::make_fastdiv((uint32_t)dec); a.n_out = (long long)n_out;
     return dispatch_fmi(f->ctx, f->fft_len, a, aeth::ctx_stream(f->ctx));
 }
-
-}  // extern "C"
-
-namespace aeth {
-
-int fir_exec_on(aeth_fir *f, hipStream_t stream, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, aeth_cf32 *out)
-{
-    FmiArgs a;
-    a.in = (const cf *)in; a.out = (cf *)out; a.hist = (const cf *)hist; a.Hf = (const cf *)f->Hf;
-    a.twN = (const cf *)f->fft->tw_dev; a.twL = (const cf *)f->fft->tw_lane_dev;
-    a.n = (long long)n; a.hop = (int)f->hop; a.ov = (int)(f->fft_len - f->hop); a.nhist = (int)(f->ntaps - 1);
-    a.nblocks = (long long)((n + f->hop - 1) / f->hop);
-    a.s_fwd = 1.0f; a.s_bwd = 1.0f;
-    return dispatch_fmi(f->ctx, f->fft_len, a, stream);
-}
-
-}  // namespace aeth
-
-extern "C" {
 
 int aeth_fir_exec_host(aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, aeth_cf32 *out)
 {
@@ -548,13 +491,14 @@ int aeth_fir_exec_host(aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, 
     const size_t bytes = n * sizeof(float2);
     int rc = aeth::ctx_stage(ctx, 0, (n + nh) * sizeof(float2)); if (rc) return rc;
     rc = aeth::ctx_stage(ctx, 1, bytes); if (rc) return rc;
-    float2 *dh = (float2 *)ctx->stage[0];
+    float2 *dh = (float2 *)ctx->stage[0].p;
+    float2 *dout = (float2 *)ctx->stage[1].p;
     float2 *din = dh + nh;     // nh*8 bytes in: keeps 8-byte alignment
     if (hist && nh) AETH_HIP(hipMemcpyAsync(dh, hist, nh * sizeof(float2), hipMemcpyHostToDevice, aeth::ctx_stream(ctx)));
     AETH_HIP(hipMemcpyAsync(din, in, bytes, hipMemcpyHostToDevice, aeth::ctx_stream(ctx)));
-    rc = aeth_fir_exec(f, hist ? (const aeth_cf32 *)dh : nullptr, (const aeth_cf32 *)din, n, (aeth_cf32 *)ctx->stage[1]);
+    rc = aeth_fir_exec(f, hist ? (const aeth_cf32 *)dh : nullptr, (const aeth_cf32 *)din, n, (aeth_cf32 *)dout);
     if (rc) return rc;
-    AETH_HIP(hipMemcpyAsync(out, ctx->stage[1], bytes, hipMemcpyDeviceToHost, aeth::ctx_stream(ctx)));
+    AETH_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, aeth::ctx_stream(ctx)));
     AETH_HIP(hipStreamSynchronize(aeth::ctx_stream(ctx)));
     return AETH_OK;
 }
@@ -604,9 +548,7 @@ int aeth_corr_exec(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *in, siz
     AETH_REQUIRE(c && c->fir, AETH_E_ARG, "corr is null");
     if (n == 0) return AETH_OK;
     const aeth_fir *f = c->fir;
-    AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!touch(out, n, in, n) && !touch(out, n, hist, f->ntaps - 1), AETH_E_ARG, "%s", kMsgFirInPlace);
-    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(out) && aeth::aligned8(hist), AETH_E_ALIGN, "%s", kMsgFirAlign);
+    if (int rc = fir_check(f, hist, in, n, out, n)) return rc;
     // always the in-order stream: a search usually follows on what was just written
     return aeth::fir_exec_on(c->fir, aeth::ctx_stream(f->ctx), hist, in, n, out);
 }
@@ -625,9 +567,9 @@ int aeth_corr_exec_levels(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *
     AETH_REQUIRE(!touch_bytes(levels, n * sizeof(float), in, n * sizeof(aeth_cf32)) &&
                  !touch_bytes(levels, n * sizeof(float), hist, (f->ntaps - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
                  "levels overlaps the input (or its history)");
-    AETH_REQUIRE(f->fft_len >= 1024 && f->fft_len <= 4096, AETH_E_UNSUPPORTED,
+    AETH_REQUIRE(fused_store_len(f->fft_len), AETH_E_UNSUPPORTED,
                  "level store: fft_len %zu (one-block-per-workgroup lengths 1024 .. 4096 only)", f->fft_len);
-    FmiArgs a = corr_args(f, hist, in, n);
+    FmiArgs a = fir_args(f, hist, in, n, nullptr);
     a.levels = levels; a.level_kind = kind;
     return dispatch_fmi(f->ctx, f->fft_len, a, aeth::ctx_stream(f->ctx));
 }
@@ -647,7 +589,7 @@ int aeth_corr_search(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *in, s
     AETH_REQUIRE(!touch_bytes(peaks, nblocks * sizeof(aeth_corr_peak), in, n * sizeof(aeth_cf32)) &&
                  !touch_bytes(peaks, nblocks * sizeof(aeth_corr_peak), hist, (f->ntaps - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
                  "peaks overlaps the input (or its history)");
-    AETH_REQUIRE(f->fft_len >= 1024 && f->fft_len <= 4096, AETH_E_UNSUPPORTED,
+    AETH_REQUIRE(fused_store_len(f->fft_len), AETH_E_UNSUPPORTED,
                  "peak search: fft_len %zu (one-block-per-workgroup lengths 1024 .. 4096 only)", f->fft_len);
     AETH_REQUIRE(nblocks < ((size_t)1 << 28), AETH_E_UNSUPPORTED, "peak search: %zu samples", n);
     aeth_ctx *ctx = f->ctx;
@@ -656,13 +598,13 @@ int aeth_corr_search(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *in, s
     const int waves = (int)(f->fft_len / 16 / 64);                              // 16 points per lane (aeth_fft_core.h: CfgFor)
     const size_t nwg = (nblocks + kFoldBlock - 1) / kFoldBlock;
     const size_t parts_bytes = nblocks * (size_t)waves * sizeof(PeakPart);
-    int rc = corr_slab_ensure(ctx, parts_bytes + nwg * sizeof(PeakBest)); if (rc) return rc;
-    PeakPart *parts = static_cast<PeakPart *>(ctx->corr_slab);
-    PeakBest *wg = reinterpret_cast<PeakBest *>(static_cast<char *>(ctx->corr_slab) + parts_bytes);
+    int rc = aeth::scratch_ensure(ctx, ctx->corr_slab, parts_bytes + nwg * sizeof(PeakBest)); if (rc) return rc;
+    PeakPart *parts = static_cast<PeakPart *>(ctx->corr_slab.p);
+    PeakBest *wg = reinterpret_cast<PeakBest *>(static_cast<char *>(ctx->corr_slab.p) + parts_bytes);
     aeth::HostIO io;
     if (best) { rc = io.open(ctx, 0, sizeof(aeth_corr_peak)); if (rc) return rc; }   // the pinned bounce buffer
     hipStream_t s = aeth::ctx_stream(ctx);
-    FmiArgs a = corr_args(f, hist, in, n);
+    FmiArgs a = fir_args(f, hist, in, n, nullptr);
     a.parts = parts;
     rc = dispatch_fmi(ctx, f->fft_len, a, s); if (rc) return rc;
     hipLaunchKernelGGL(corr_fold_kernel, dim3((unsigned)nwg), dim3(kFoldBlock), 0, s, (const PeakPart *)parts, (long long)nblocks,

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdint>
@@ -10,7 +11,14 @@
 
 #include "../../include/aether_hip.h"
 
-namespace aeth { struct PipeState; }
+namespace aeth {
+struct PipeState;
+// one device buffer a context keeps between calls: grown on demand (scratch_ensure), given back by aeth_ctx_trim
+struct DevScratch {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+}  // namespace aeth
 
 struct aeth_ctx {
     int device = 0;
@@ -37,19 +45,16 @@ struct aeth_ctx {
     // host pipeline (aeth_fir_stream_host): stage streams, device slots, events, pinned staging pool, copy threads --
     // created on its first run and kept (aeth_host.h)
     aeth::PipeState *pipe = nullptr;
-    // device scratch of the host-slice flavours, grown on demand
-    void *stage[2] = {nullptr, nullptr};
-    size_t stage_bytes[2] = {0, 0};
+    // Device scratch, one buffer per user -- they are held at the same time (aeth_fir_exec_host keeps both staging slots
+    // across its launch; aeth_corr_search keeps its slab while HostIO may hold stage[1]):
+    //   stage[2]    the host-slice flavours' input / output (ctx_stage)
+    //   stats_slab  per-workgroup partial records of aeth_vec_stats (aeth_stats.hip)
+    //   corr_slab   per-wave and per-workgroup records of aeth_corr_search (aeth_fir.hip)
+    aeth::DevScratch stage[2], stats_slab, corr_slab;
     // small host-slice calls: two pinned, device-visible bounce buffers (aeth::HostIO)
     void *bounce[2] = {nullptr, nullptr};
     // plans of the one-shot vec_fft / vec_ifft (aeth_fft.hip: fft_cache_get), most recently used first
     void *fft_cache = nullptr;
-    // per-workgroup partial records of aeth_vec_stats (aeth_stats.hip), grown on demand, released by aeth_ctx_trim
-    void *stats_slab = nullptr;
-    size_t stats_slab_bytes = 0;
-    // per-wave and per-workgroup records of aeth_corr_search (aeth_fir.hip), grown on demand, released by aeth_ctx_trim
-    void *corr_slab = nullptr;
-    size_t corr_slab_bytes = 0;
 };
 
 namespace aeth {
@@ -65,14 +70,20 @@ inline hipStream_t ctx_stream(const aeth_ctx *ctx) { return ctx_stream(const_cas
 // previous call on this context was such a launch and the buffers are disjoint, else the main stream.
 hipStream_t ctx_fir_lane(aeth_ctx *ctx, uintptr_t in_lo, uintptr_t in_hi, uintptr_t out_lo, uintptr_t out_hi);
 
-// ensure staging slot `i` holds >= bytes of device memory
-int ctx_stage(aeth_ctx *ctx, int i, size_t bytes);
+// Ensure `s` holds >= bytes of device memory: nothing happens when it already does; else it is replaced by a buffer of
+// bytes + bytes/4.  The context's stream is waited for before the old buffer is freed.  (The staging slots used to be
+// freed without that wait: hipFree waits for the device itself and the host-slice calls are synchronous, so the
+// explicit wait changes nothing observable there.)
+int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes);
+// frees it; on a failed free the buffer stays recorded and the HIP error is returned (aeth_ctx_trim reports it,
+// aeth_ctx_destroy does not)
+hipError_t scratch_release(DevScratch &s);
+// every scratch buffer of the context
+inline std::array<DevScratch *, 4> ctx_scratch(aeth_ctx *ctx) { return {&ctx->stage[0], &ctx->stage[1], &ctx->stats_slab, &ctx->corr_slab}; }
+// ensure staging slot `i` holds >= bytes of device memory (an unused slot still gets 16 bytes)
+inline int ctx_stage(aeth_ctx *ctx, int i, size_t bytes) { return scratch_ensure(ctx, ctx->stage[i], bytes ? bytes : 16); }
 // frees the plans vec_fft / vec_ifft built for this context (aeth_ctx_destroy, aeth_ctx_trim)
 void fft_cache_release(aeth_ctx *ctx);
-// frees the slab of aeth_vec_stats (aeth_ctx_destroy, aeth_ctx_trim)
-void stats_slab_release(aeth_ctx *ctx);
-// frees the slab of aeth_corr_search (aeth_ctx_destroy, aeth_ctx_trim)
-void corr_slab_release(aeth_ctx *ctx);
 
 // Buffers of one host-slice call (the literal trait call: host slice in, host slice out, synchronous).
 //   small (every buffer <= kZeroCopyMax): the context's two pinned, device-visible bounce buffers -- memcpy in, the kernel

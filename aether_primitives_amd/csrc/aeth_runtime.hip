@@ -106,17 +106,25 @@ hipStream_t ctx_fir_lane(aeth_ctx *ctx, uintptr_t in_lo, uintptr_t in_hi, uintpt
     return s;
 }
 
-int ctx_stage(aeth_ctx *ctx, int i, size_t bytes)
+int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes)
 {
+    if (s.bytes >= bytes) return AETH_OK;
     DeviceGuard dev_guard(ctx->device);
-    if (bytes == 0) bytes = 16;
-    if (ctx->stage_bytes[i] < bytes) {
-        size_t want = bytes + bytes / 4;
-        if (ctx->stage[i]) { AETH_HIP(hipFree(ctx->stage[i])); ctx->stage[i] = nullptr; ctx->stage_bytes[i] = 0; }
-        AETH_HIP(hipMalloc(&ctx->stage[i], want));
-        ctx->stage_bytes[i] = want;
+    if (s.p) {
+        AETH_HIP(hipStreamSynchronize(ctx_stream(ctx)));
+        AETH_HIP(scratch_release(s));
     }
+    const size_t want = bytes + bytes / 4;
+    AETH_HIP(hipMalloc(&s.p, want));
+    s.bytes = want;
     return AETH_OK;
+}
+
+hipError_t scratch_release(DevScratch &s)
+{
+    const hipError_t e = s.p ? hipFree(s.p) : hipSuccess;
+    if (e == hipSuccess) s = DevScratch{};
+    return e;
 }
 
 int HostIO::open(aeth_ctx *c, size_t bytes0, size_t bytes1)
@@ -131,7 +139,7 @@ int HostIO::open(aeth_ctx *c, size_t bytes0, size_t bytes1)
             buf[i] = c->bounce[i];
         } else {
             int rc = ctx_stage(c, i, want[i]); if (rc) return rc;
-            buf[i] = c->stage[i];
+            buf[i] = c->stage[i].p;
         }
     }
     return AETH_OK;
@@ -254,14 +262,11 @@ int aeth_ctx_destroy(aeth_ctx *ctx)
     aeth::DeviceGuard g(ctx->device);
     (void)hipStreamSynchronize(aeth::ctx_stream(ctx));
     aeth::fft_cache_release(ctx);
-    aeth::stats_slab_release(ctx);
-    aeth::corr_slab_release(ctx);
     overlap_release(ctx);
     aeth::pipe_release(ctx);
-    for (int i = 0; i < 2; i++) {
-        if (ctx->stage[i]) (void)hipFree(ctx->stage[i]);
+    for (aeth::DevScratch *s : aeth::ctx_scratch(ctx)) (void)aeth::scratch_release(*s);
+    for (int i = 0; i < 2; i++)
         if (ctx->bounce[i]) (void)hipHostFree(ctx->bounce[i]);
-    }
     if (ctx->owns_stream && ctx->stream_main) (void)hipStreamDestroy(ctx->stream_main);
     delete ctx;
     return AETH_OK;

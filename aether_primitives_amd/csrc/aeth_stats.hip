@@ -185,27 +185,13 @@ __global__ __launch_bounds__(kBlock) void levels_kernel(const float2 *__restrict
     }
 }
 
-int slab_ensure(aeth_ctx *ctx, size_t bytes)
-{
-    if (ctx->stats_slab_bytes >= bytes) return AETH_OK;
-    if (ctx->stats_slab) {
-        AETH_HIP(hipStreamSynchronize(aeth::ctx_stream(ctx)));
-        AETH_HIP(hipFree(ctx->stats_slab));
-        ctx->stats_slab = nullptr; ctx->stats_slab_bytes = 0;
-    }
-    const size_t want = bytes + bytes / 4;
-    AETH_HIP(hipMalloc(&ctx->stats_slab, want));
-    ctx->stats_slab_bytes = want;
-    return AETH_OK;
-}
-
 // x_dev: device-visible memory; io.buf[1] receives the final record (pinned host memory or the context's staging)
 int stats_run(aeth_ctx *ctx, aeth::HostIO &io, const aeth_cf32 *x_dev, size_t n, struct aeth_vec_stats *out)
 {
     const size_t nrec = (n + kChunk - 1) / kChunk;
     AETH_REQUIRE(nrec <= 0x7fffffffu, AETH_E_UNSUPPORTED, "%zu samples", n);
-    int rc = slab_ensure(ctx, nrec * sizeof(Rec)); if (rc) return rc;
-    Rec *slab = static_cast<Rec *>(ctx->stats_slab);
+    int rc = aeth::scratch_ensure(ctx, ctx->stats_slab, nrec * sizeof(Rec)); if (rc) return rc;
+    Rec *slab = static_cast<Rec *>(ctx->stats_slab.p);
     const float2 *x = reinterpret_cast<const float2 *>(x_dev);
     const bool nt = aeth::streams_past_cache(n * sizeof(float2));
     hipStream_t s = aeth::ctx_stream(ctx);
@@ -236,15 +222,6 @@ void launch_levels(aeth_ctx *ctx, const float2 *x, float *lv, size_t n, bool nt)
 }
 
 }  // namespace
-
-namespace aeth {
-void stats_slab_release(aeth_ctx *ctx)
-{
-    if (ctx->stats_slab) (void)hipFree(ctx->stats_slab);
-    ctx->stats_slab = nullptr;
-    ctx->stats_slab_bytes = 0;
-}
-}  // namespace aeth
 
 extern "C" {
 

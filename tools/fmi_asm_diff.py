@@ -3,7 +3,10 @@
 
     hipcc <the flags of csrc/Makefile for aeth_fir.hip> --cuda-device-only -S aeth_fir.hip -o old.s     (at the old revision)
     hipcc ...                                                               -o new.s                   (at the new one)
-    tools/fmi_asm_diff.py old.s new.s [substring of a mangled name ...]
+    tools/fmi_asm_diff.py [--family=SUBSTRING] old.s new.s [substring of a mangled name ...]
+
+--family: the kernels compared are those whose mangled name contains SUBSTRING (default: fmi_kernel), so that other
+families (corr_, stats_, levels_ ...) are checked with the same tool.
 
 Every fmi_kernel instantiation present in both files is compared instruction by instruction after what a new neighbour
 in the translation unit changes has been normalised away: comments, and the function's ordinal in its local labels
@@ -57,11 +60,14 @@ def hidden_arg_moved(x, y, explicit_old, grow):
 
 
 def main():
-    old, new, pats = sys.argv[1], sys.argv[2], sys.argv[3:]
+    argv, family = sys.argv[1:], "fmi_kernel"
+    if argv and argv[0].startswith("--family="):
+        family, argv = argv[0].split("=", 1)[1], argv[1:]
+    old, new, pats = argv[0], argv[1], argv[2:]
     a, b, ma, mb = funcs(old), funcs(new), meta(old), meta(new)
     same = diff = 0
     for k in sorted(a):
-        if "fmi_kernel" not in k:
+        if family not in k:
             continue
         if k not in b:
             print("ONLY IN OLD", k)
@@ -83,8 +89,8 @@ def main():
             print("IDENTICAL" if eq else "DIFFERENT", k, f"instructions {n}, sha1 {h[0]} / {h[1]}, hidden-argument loads moved: {moved};",
                   "descriptor:", ma.get(k),
                   "changed fields (old, new):", changed)
-    added = len([k for k in b if "fmi_kernel" in k and k not in a])
-    print(f"fmi_kernel builds in old: {same + diff}; identical code: {same}; different: {diff}; builds only in new: {added}")
+    added = len([k for k in b if family in k and k not in a])
+    print(f"{family} builds in old: {same + diff}; identical code: {same}; different: {diff}; builds only in new: {added}")
     return 1 if diff else 0
 
 
