@@ -173,6 +173,18 @@ PROTOTYPES = {
     "aeth_chan_exec": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, vp, sz]),
     "aeth_chan_exec_levels": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, i32, i32, vp, sz]),
     "aeth_chan_prototype": (i32, [i32, sz, sz, vp]),
+    "aeth_synth_create": (i32, [vp, vp, sz, sz, sz, i32, sz, pvp]),
+    "aeth_synth_destroy": (i32, [vp]),
+    "aeth_synth_channels": (sz, [vp]),
+    "aeth_synth_ntaps": (sz, [vp]),
+    "aeth_synth_hop": (sz, [vp]),
+    "aeth_synth_phase": (i32, [vp]),
+    "aeth_synth_route": (C.c_char_p, [vp]),
+    "aeth_synth_tile": (sz, [vp]),
+    "aeth_synth_history": (sz, [vp]),
+    "aeth_synth_unfold": (i32, [vp, vp, vp, sz, u64, vp, sz]),
+    "aeth_synth_exec": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, vp, sz]),
+    "aeth_synth_dual_window": (i32, [vp, sz, sz, vp]),
 }
 
 _lib = None

@@ -10,6 +10,7 @@
 //   general  everything else: a lane owns output q of frame m and reads its P inputs at r = (q - rot) mod M; the
 //            M / D-fold (and, for hop == M with P > 8, the P-fold) overlap is served by L2.
 #include "aeth_internal.h"
+#include "aeth_chan_fold.h"
 #include "aeth_fft_plan.h"
 #include "aeth_levels.h"
 
@@ -162,18 +163,6 @@ bool touch_bytes(const void *a, size_t na, const void *b, size_t nb)
 
 }  // namespace
 
-struct aeth_chan {
-    aeth_ctx *ctx = nullptr;
-    size_t M = 0, L = 0, P = 0, D = 0;
-    int phase = 0;
-    bool ring = false;           // hop == M and P <= kRingMaxP
-    size_t tile = 0;
-    float *w_dev = nullptr;
-    aeth_fft *fft = nullptr;
-    float2 *scratch = nullptr;   // the folded frames of exec / exec_levels, grown on demand
-    size_t scratch_elems = 0;
-};
-
 namespace {
 
 int ensure_scratch(aeth_chan *c, size_t elems)
@@ -191,8 +180,10 @@ int ensure_scratch(aeth_chan *c, size_t elems)
     return AETH_OK;
 }
 
+}  // namespace
+
 // workgroups of a launch over F frames, at most (the ring kernel with one column per lane)
-size_t grid_bound(const aeth_chan *c, size_t F)
+size_t aeth::chan_grid_bound(const aeth_chan *c, size_t F)
 {
     const size_t ntiles = (F + c->tile - 1) / c->tile;
     if (!c->ring) return ntiles * ((c->M + kGenElems - 1) / kGenElems);
@@ -200,6 +191,20 @@ size_t grid_bound(const aeth_chan *c, size_t F)
     while (lx < (size_t)kBlock && lx < c->M) lx *= 2;
     return ((ntiles + kBlock / lx - 1) / (kBlock / lx)) * ((c->M + lx - 1) / lx);
 }
+
+void aeth::chan_geometry(aeth_chan *c)
+{
+    c->ring = c->D == c->M && c->P <= kRingMaxP;
+    if (c->ring) {
+        // P - 1 halo rows per tile: a sixteenth of the tile at most (P = 2: 1 of 16, P = 8: 7 of 128)
+        c->tile = 16;
+        while (c->tile < 16 * (c->P - 1)) c->tile *= 2;
+    } else {
+        c->tile = c->M <= kGenElems / 2 ? kGenElems / c->M : 1;
+    }
+}
+
+namespace {
 
 // what every exec call checks before any device work; out_elem_bytes: size of the caller's output range
 int check_call(const aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, const void *out, size_t n_out,
@@ -217,12 +222,14 @@ int check_call(const aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, s
     AETH_REQUIRE(!touch_bytes(out, n_out * out_elem_bytes, in, n * sizeof(aeth_cf32)) &&
                  !touch_bytes(out, n_out * out_elem_bytes, hist, (c->L - c->D) * sizeof(aeth_cf32)), AETH_E_ARG,
                  "the output range overlaps the input (or its history)");
-    AETH_REQUIRE(grid_bound(c, F) < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu frames in one call: more than 2^31 workgroups", F);
+    AETH_REQUIRE(aeth::chan_grid_bound(c, F) < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu frames in one call: more than 2^31 workgroups", F);
     *nframes = F;
     return AETH_OK;
 }
 
-int launch_fold(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t F, uint64_t first_frame, float2 *out)
+}  // namespace
+
+int aeth::chan_launch_fold(const aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t F, uint64_t first_frame, float2 *out)
 {
     ChanCall a{};
     a.in = (const float2 *)in;
@@ -259,8 +266,6 @@ int launch_fold(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t
     AETH_HIP(hipGetLastError());
     return AETH_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -314,14 +319,7 @@ int aeth_chan_create(aeth_ctx *ctx, const float *proto_host, size_t ntaps, size_
     if (!c) { (void)aeth_fft_destroy(fft); return aeth::set_error(AETH_E_NOMEM, "out of host memory"); }
     c->ctx = ctx; c->fft = fft;
     c->M = channels; c->L = ntaps; c->P = ntaps / channels; c->D = hop; c->phase = phase;
-    c->ring = hop == channels && c->P <= kRingMaxP;
-    if (c->ring) {
-        // P - 1 halo rows per tile: a sixteenth of the tile at most (P = 2: 1 of 16, P = 8: 7 of 128)
-        c->tile = 16;
-        while (c->tile < 16 * (c->P - 1)) c->tile *= 2;
-    } else {
-        c->tile = channels <= kGenElems / 2 ? kGenElems / channels : 1;
-    }
+    aeth::chan_geometry(c);
     aeth::DeviceGuard dg(ctx->device);
     hipError_t e = hipMalloc((void **)&c->w_dev, ntaps * sizeof(float));
     if (e == hipSuccess) e = hipMemcpyAsync(c->w_dev, proto_host, ntaps * sizeof(float), hipMemcpyHostToDevice, aeth::ctx_stream(ctx));
@@ -358,7 +356,7 @@ int aeth_chan_fold(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, siz
 {
     size_t F = 0;
     int rc = check_call(c, hist, in, n, out, n_out, sizeof(aeth_cf32), &F); if (rc) return rc;
-    return launch_fold(c, hist, in, F, first_frame, (float2 *)out);
+    return aeth::chan_launch_fold(c, hist, in, F, first_frame, (float2 *)out);
 }
 
 int aeth_chan_exec(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, uint64_t first_frame, int sign,
@@ -369,7 +367,7 @@ int aeth_chan_exec(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, siz
     AETH_REQUIRE(sign == AETH_SIGN_REF_FWD || sign == AETH_SIGN_REF_BWD, AETH_E_ARG, "sign must be +1 or -1");
     AETH_REQUIRE(scale_kind >= AETH_SCALE_NONE && scale_kind <= AETH_SCALE_X, AETH_E_ARG, "bad scale kind %d", scale_kind);
     rc = ensure_scratch(c, n_out); if (rc) return rc;
-    rc = launch_fold(c, hist, in, F, first_frame, c->scratch); if (rc) return rc;
+    rc = aeth::chan_launch_fold(c, hist, in, F, first_frame, c->scratch); if (rc) return rc;
     return aeth_fft_exec(c->fft, (const aeth_cf32 *)c->scratch, n_out, out, F, sign, scale_kind, x);
 }
 
@@ -382,7 +380,7 @@ int aeth_chan_exec_levels(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *
     AETH_REQUIRE(scale_kind >= AETH_SCALE_NONE && scale_kind <= AETH_SCALE_X, AETH_E_ARG, "bad scale kind %d", scale_kind);
     AETH_REQUIRE(aeth::level_kind_ok(level_kind), AETH_E_ARG, "bad level kind %d", level_kind);
     rc = ensure_scratch(c, n_levels); if (rc) return rc;
-    rc = launch_fold(c, hist, in, F, first_frame, c->scratch); if (rc) return rc;
+    rc = aeth::chan_launch_fold(c, hist, in, F, first_frame, c->scratch); if (rc) return rc;
     return aeth_fft_exec_levels(c->fft, (const aeth_cf32 *)c->scratch, n_levels, F, sign, scale_kind, x, mirror, level_kind, levels,
                                 n_levels);
 }

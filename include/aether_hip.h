@@ -51,6 +51,7 @@ typedef struct aeth_fir aeth_fir;       /* gives Fir<T> (src/fir.rs:3-22) a body
 typedef struct aeth_corr aeth_corr;     /* streaming correlator: a matched filter with fused level / peak stores */
 typedef struct aeth_seq aeth_seq;       /* LFSR sequences: sequence::generate (src/sequence.rs:47-53) for linear generators */
 typedef struct aeth_chan aeth_chan;     /* polyphase analysis filter bank: windowed, overlapped frames in front of aeth_fft */
+typedef struct aeth_synth aeth_synth;   /* polyphase synthesis filter bank: weighted overlap-add behind aeth_fft */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -501,6 +502,72 @@ AETH_API int aeth_chan_exec_levels(aeth_chan *chan, const aeth_cf32 *hist_dev, c
  *                 divided by its f64 sum (unit DC gain); L = 1 gives 1
  * A bad kind or a zero size: AETH_E_ARG. */
 AETH_API int aeth_chan_prototype(int kind, size_t channels, size_t taps_per_channel, float *out_host);
+
+/* ---- polyphase synthesis filter bank (no body in the reference) -------------------------------- */
+/* The transpose of aeth_chan: what puts a stream back together after aeth_chan_exec took it apart (the reference only
+ * takes apart: `waterfall`, src/util/plot.rs:46-68).  Every frame's M time samples (an inverse transform of its M bins)
+ * are extended periodically to L = P * M, weighted by a synthesis prototype and overlap-added at the hop D:
+ *   P = 1, D < M   the inverse STFT (weighted overlap-add)     P > 1   the polyphase synthesis bank, a transmultiplexer
+ * An aeth_synth is made of a REAL prototype g[0 .. L) (host floats, copied), channels = M, hop = D and a phase mode
+ * (AETH_CHAN_PHASE_FRAME / _STREAM).  L = ntaps is a multiple of M, P = L / M in 1 .. 64, D in 1 .. M.
+ * K = ceil(L / D) frames touch one output sample; K > 256 is refused (AETH_E_UNSUPPORTED).
+ *
+ * The frames: v_m[q] = frames_dev[m * M + q] for m = 0 .. F - 1, n_in = F * M.  The K - 1 frames in front of them,
+ * m = -(K - 1) .. -1, are hist_dev[(m + K - 1) * M + q] (oldest frame first), or frames of +0.0 when hist_dev is NULL:
+ * those are multiplied like any other frame.  hist_dev is ignored when K == 1.  The call writes F * D samples.
+ *
+ * The overlap-add is defined bit for bit (f32, no contraction).  For i = 0 .. F * D - 1:
+ *     out[i] = sum over m, ascending, with 0 <= i - m * D < L, of  g[j] * v_m[(j + rot_m) mod M],   j = i - m * D
+ * every product rounded, the sum started from the first product (not from +0), products added oldest frame first, re and
+ * im independently, each as a real multiplication by g[j].  A frame that does not reach i adds nothing, not even a zero.
+ *   AETH_CHAN_PHASE_FRAME   rot_m = 0.
+ *   AETH_CHAN_PHASE_STREAM  rot_m = ((G + 1) * D) mod M with G = first_frame + m reduced modulo M (to 0 .. M - 1, also
+ *                           for the history's frame numbers below zero when first_frame is 0).  rot is 0 when D == M.
+ * This is the transpose of aeth_chan_fold: the analysis' frame m covers s[(m + 1) * D - L + j], the synthesis puts it at
+ * m * D + j, so the output is the reconstruction DELAYED by L - D samples.  Every output is complete within its call:
+ * the chunks of a stream concatenate exactly when the caller passes the previous K - 1 frames as history.
+ *
+ * All calls are ordered on the context's in-order stream and validate everything before any device work: NULL pointers
+ * AETH_E_ARG; n_in == 0, n_in not a multiple of M, or n_out other than F * D AETH_E_LEN; pointers 8-byte aligned
+ * (AETH_E_ALIGN); the output range clear of the input and the history (AETH_E_ARG).  Element counts are size_t. */
+/* No body in the reference (src/util/plot.rs:46-68 never resynthesizes).  The inner plan is made by
+ * aeth_fft_create(ctx, channels, ...): a transform length it refuses fails here with its code and its message naming the
+ * length, and nothing stays allocated.  P > 64 or K > 256: AETH_E_UNSUPPORTED; any other violation of the rules above:
+ * AETH_E_ARG.  max_frames > 0 sizes the scratch of exec at creation; it grows on demand like the plan's. */
+AETH_API int aeth_synth_create(aeth_ctx *ctx, const float *proto_host, size_t ntaps, size_t channels, size_t hop, int phase,
+                               size_t max_frames, aeth_synth **out);
+/* No body in the reference (src/util/plot.rs:46-68 frames without an object).  Waits for the context's stream. */
+AETH_API int aeth_synth_destroy(aeth_synth *synth);
+/* No body in the reference (src/util/plot.rs:46-68: fft_len is an argument there): M, L, D and the phase mode. */
+AETH_API size_t aeth_synth_channels(const aeth_synth *synth);
+AETH_API size_t aeth_synth_ntaps(const aeth_synth *synth);
+AETH_API size_t aeth_synth_hop(const aeth_synth *synth);
+AETH_API int aeth_synth_phase(const aeth_synth *synth);
+/* No body in the reference (src/util/plot.rs:46-68 plans inside the call): the inner plan's aeth_fft_route text, owned
+ * by the object. */
+AETH_API const char *aeth_synth_route(const aeth_synth *synth);
+/* No body in the reference (src/util/plot.rs:46-68): consecutive hops one lane (D == M with P <= 8, or D < M dividing L
+ * with K <= 8) or one workgroup (every other shape) makes, like aeth_chan_tile: the launch geometry, for tests that
+ * want to cross its edges. */
+AETH_API size_t aeth_synth_tile(const aeth_synth *synth);
+/* No body in the reference (src/util/plot.rs:46-68 has no overlap): K - 1, the frames of history a call reads. */
+AETH_API size_t aeth_synth_history(const aeth_synth *synth);
+/* No body in the reference (src/util/plot.rs:46-68 has no way back to a stream): the back end alone, as defined above.
+ * 8 * M bytes read and 8 * D written per frame when every frame comes from HBM once. */
+AETH_API int aeth_synth_unfold(aeth_synth *synth, const aeth_cf32 *hist_dev, const aeth_cf32 *frames_dev, size_t n_in,
+                               uint64_t first_frame, aeth_cf32 *out_dev, size_t n_out);
+/* No body in the reference (src/util/plot.rs:46-68 only transforms forward): hist_dev and spec_dev hold SPECTRA.
+ * aeth_fft_exec of the K - 1 history frames (when given) and of the F frames into the object's scratch of
+ * (K - 1 + F) * M samples, then the unfold; bit-identical to those aeth_fft_exec calls followed by aeth_synth_unfold. */
+AETH_API int aeth_synth_exec(aeth_synth *synth, const aeth_cf32 *hist_dev, const aeth_cf32 *spec_dev, size_t n_in,
+                             uint64_t first_frame, int sign, int scale_kind, float x, aeth_cf32 *out_dev, size_t n_out);
+/* No body in the reference (src/util/plot.rs:46-68 has no window).  Host only, needs no context: the synthesis window
+ * that inverts a windowed, overlapped transform (P = 1, ntaps = M), j = 0 .. ntaps - 1:
+ *     g[j] = w[j] / sum over j' = j (mod hop), 0 <= j' < ntaps, of w[j']^2
+ * computed in f64 and rounded once to f32.  With it aeth_chan_exec (sign -1) followed by aeth_synth_exec (sign +1,
+ * AETH_SCALE_N) returns the stream, delayed by ntaps - hop.  A null pointer, a zero size, hop > ntaps or a denominator
+ * below 2^-20 (the periodic Hann window at hop == ntaps): AETH_E_ARG, the message names j; nothing is written. */
+AETH_API int aeth_synth_dual_window(const float *w, size_t ntaps, size_t hop, float *out_host);
 
 /* ---- pinned host buffers: src/pool.rs:43-221 -------------------------------------------------- */
 /* The reference's object pool ("useful for large buffers and other time expensive objects", :9-10) with pinned

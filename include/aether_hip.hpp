@@ -505,6 +505,52 @@ private:
     aeth_chan *h_ = nullptr;
 };
 
+// ---- polyphase synthesis filter bank (no body in the reference: src/util/plot.rs:46-68 only takes a stream apart) ------
+// The transpose of Channelizer: every frame's `channels` time samples are extended periodically to proto.size(), weighted
+// and overlap-added at `hop`; the output is the reconstruction delayed by proto.size() - hop samples.
+class Synthesizer {
+public:
+    Synthesizer(Context &ctx, const std::vector<float> &proto, size_t channels, size_t hop = 0, int phase = AETH_CHAN_PHASE_FRAME,
+                size_t max_frames = 0)
+    {
+        check(aeth_synth_create(ctx.get(), proto.data(), proto.size(), channels, hop ? hop : channels, phase, max_frames, &h_));
+    }
+    ~Synthesizer() { aeth_synth_destroy(h_); }
+    Synthesizer(const Synthesizer &) = delete;
+    Synthesizer &operator=(const Synthesizer &) = delete;
+    // the synthesis window that inverts a windowed, overlapped transform of w.size() points at `hop`, computed on the host
+    static std::vector<float> dual_window(const std::vector<float> &w, size_t hop)
+    {
+        std::vector<float> g(w.size());
+        check(aeth_synth_dual_window(w.data(), w.size(), hop, g.data()));
+        return g;
+    }
+    size_t channels() const { return aeth_synth_channels(h_); }
+    size_t ntaps() const { return aeth_synth_ntaps(h_); }
+    size_t hop() const { return aeth_synth_hop(h_); }
+    int phase() const { return aeth_synth_phase(h_); }
+    size_t tile() const { return aeth_synth_tile(h_); }
+    size_t history() const { return aeth_synth_history(h_); }
+    std::string route() const { return aeth_synth_route(h_); }
+    size_t samples(size_t n_in) const { return n_in / channels() * hop(); }
+    // `hist`: the history() frames in front of `frames` (null: zeros); first_frame: the global number of the call's first frame
+    void unfold(const DeviceVec &frames, DeviceVec &out, const DeviceVec *hist = nullptr, uint64_t first_frame = 0)
+    {
+        check(aeth_synth_unfold(h_, hist ? hist->ptr() : nullptr, frames.ptr(), frames.len(), first_frame, out.ptr(), out.len()));
+    }
+    // `spec` and `hist` hold spectra: the transform of every frame, then the overlap-add
+    void exec(const DeviceVec &spec, DeviceVec &out, Scale s, const DeviceVec *hist = nullptr, uint64_t first_frame = 0,
+              int sign = AETH_SIGN_REF_BWD)
+    {
+        check(aeth_synth_exec(h_, hist ? hist->ptr() : nullptr, spec.ptr(), spec.len(), first_frame, sign, s.kind, s.x, out.ptr(),
+                              out.len()));
+    }
+    aeth_synth *get() const { return h_; }
+
+private:
+    aeth_synth *h_ = nullptr;
+};
+
 // ---- sequence::expand / sequence::generate for linear generators (src/sequence.rs:18-53) ----------------------------
 // A register is the set of its delays: seq[n] = XOR seq[n - d]; 1 .. 4 registers XORed (Gold codes: two).  `init` holds
 // one word per register, bit i = seq[i] (what expand() unpacks).  Device pointers in and out; bits are one byte each.

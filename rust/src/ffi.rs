@@ -9,6 +9,7 @@ use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_corr { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_seq { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_chan { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_synth { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
 pub const AETH_POOL_ZERO_ON_RETURN: c_int = 1;
@@ -199,6 +200,21 @@ extern "C" {
                                  sign: c_int, scale_kind: c_int, x: c_float, mirror: c_int, level_kind: c_int,
                                  levels_dev: *mut c_float, n_levels: usize) -> c_int;
     pub fn aeth_chan_prototype(kind: c_int, channels: usize, taps_per_channel: usize, out_host: *mut c_float) -> c_int;
+    pub fn aeth_synth_create(ctx: *mut aeth_ctx, proto_host: *const c_float, ntaps: usize, channels: usize, hop: usize, phase: c_int,
+                             max_frames: usize, out: *mut *mut aeth_synth) -> c_int;
+    pub fn aeth_synth_destroy(synth: *mut aeth_synth) -> c_int;
+    pub fn aeth_synth_channels(synth: *const aeth_synth) -> usize;
+    pub fn aeth_synth_ntaps(synth: *const aeth_synth) -> usize;
+    pub fn aeth_synth_hop(synth: *const aeth_synth) -> usize;
+    pub fn aeth_synth_phase(synth: *const aeth_synth) -> c_int;
+    pub fn aeth_synth_route(synth: *const aeth_synth) -> *const c_char;
+    pub fn aeth_synth_tile(synth: *const aeth_synth) -> usize;
+    pub fn aeth_synth_history(synth: *const aeth_synth) -> usize;
+    pub fn aeth_synth_unfold(synth: *mut aeth_synth, hist_dev: *const cf32, frames_dev: *const cf32, n_in: usize, first_frame: u64,
+                             out_dev: *mut cf32, n_out: usize) -> c_int;
+    pub fn aeth_synth_exec(synth: *mut aeth_synth, hist_dev: *const cf32, spec_dev: *const cf32, n_in: usize, first_frame: u64,
+                           sign: c_int, scale_kind: c_int, x: c_float, out_dev: *mut cf32, n_out: usize) -> c_int;
+    pub fn aeth_synth_dual_window(w: *const c_float, ntaps: usize, hop: usize, out_host: *mut c_float) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;

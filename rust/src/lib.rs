@@ -302,6 +302,42 @@ impl<'c> Channelizer<'c> {
 }
 impl<'c> Drop for Channelizer<'c> { fn drop(&mut self) { unsafe { aeth_chan_destroy(self.h); } } }
 
+/// Polyphase synthesis filter bank (no body in the reference: src/util/plot.rs:46-68 only takes a stream apart), the
+/// transpose of `Channelizer`: every frame's `channels` time samples are extended periodically to `proto.len()`, weighted
+/// and overlap-added at `hop`.  The output is the reconstruction delayed by `proto.len() - hop` samples.
+pub struct Synthesizer<'c> { h: *mut aeth_synth, _ctx: PhantomData<&'c Context> }
+impl<'c> Synthesizer<'c> {
+    pub fn new(ctx: &'c Context, proto: &[f32], channels: usize, hop: usize, stream_phase: bool) -> Synthesizer<'c> {
+        let mut h = ptr::null_mut();
+        let phase = if stream_phase { AETH_CHAN_PHASE_STREAM } else { AETH_CHAN_PHASE_FRAME };
+        check(unsafe { aeth_synth_create(ctx.h, proto.as_ptr(), proto.len(), channels, hop, phase, 0, &mut h) });
+        Synthesizer { h, _ctx: PhantomData }
+    }
+    /// the synthesis window that inverts a windowed, overlapped transform of `w.len()` points at `hop`
+    pub fn dual_window(w: &[f32], hop: usize) -> Vec<f32> {
+        let mut g = vec![0f32; w.len()];
+        check(unsafe { aeth_synth_dual_window(w.as_ptr(), w.len(), hop, g.as_mut_ptr()) });
+        g
+    }
+    pub fn channels(&self) -> usize { unsafe { aeth_synth_channels(self.h) } }
+    pub fn hop(&self) -> usize { unsafe { aeth_synth_hop(self.h) } }
+    /// frames in front of a call's first that reach into its output
+    pub fn history(&self) -> usize { unsafe { aeth_synth_history(self.h) } }
+    pub fn samples(&self, n_in: usize) -> usize { n_in / self.channels() * self.hop() }
+    /// the overlap-add alone; `hist`: the history() frames in front of `frames` (None: zeros)
+    pub fn unfold(&mut self, frames: &DeviceVec, hist: Option<&DeviceVec>, first_frame: u64, out: &mut DeviceVec) {
+        check(unsafe { aeth_synth_unfold(self.h, hist.map_or(ptr::null(), |h| h.p as *const cf32), frames.p, frames.n, first_frame,
+                                         out.p, out.n) });
+    }
+    /// `bwd` with Scale `s` on every frame of `spec` (and of `hist`: both hold spectra), then the overlap-add
+    pub fn exec(&mut self, spec: &DeviceVec, hist: Option<&DeviceVec>, first_frame: u64, s: Scale, out: &mut DeviceVec) {
+        let (kind, xs) = scale_args(s);
+        check(unsafe { aeth_synth_exec(self.h, hist.map_or(ptr::null(), |h| h.p as *const cf32), spec.p, spec.n, first_frame,
+                                       AETH_SIGN_REF_BWD, kind, xs, out.p, out.n) });
+    }
+}
+impl<'c> Drop for Synthesizer<'c> { fn drop(&mut self) { unsafe { aeth_synth_destroy(self.h); } } }
+
 /// The device counterpart of `pipeline::new().add_stage(..)` (src/pipeline.rs:24-41, :123-137): five fixed stages --
 /// copy-in | upload | compute | download | copy-out -- whose compute stage is one of the library's device ops (a closure
 /// cannot cross the C ABI).  `run` takes host slices and returns what `aeth_stream_host` reports.
