@@ -29,10 +29,9 @@ def prototype(kind, channels, taps_per_channel):
     return out[:channels * taps_per_channel]
 
 
-class Channelizer:
-    """Channelizer(ctx, proto, channels, hop=None, phase="frame"): `proto` holds P * channels real taps, hop defaults to
-    `channels`.  phase="frame": every frame's phase refers to its own first sample (STFT); phase="stream": to the
-    first sample ever fed (pass the global number of a call's first frame as `first_frame`)."""
+class _Bank:
+    """what Channelizer and Synthesizer share: the handle's life, its read-outs, the coercion of a call's vectors"""
+    _prefix = None                                 # of the C names: "aeth_chan_" / "aeth_synth_"
 
     def __init__(self, ctx, proto, channels, hop=None, phase=PHASE_FRAME, max_frames=0):
         self.ctx = ctx
@@ -41,43 +40,57 @@ class Channelizer:
         hop = channels if hop is None else hop
         phase = _PHASES[phase.lower()] if isinstance(phase, str) else int(phase)
         h = C.c_void_p()
-        check(self._lib.aeth_chan_create(ctx.h, proto.ctypes.data_as(C.c_void_p), proto.size, int(channels), int(hop), phase,
-                                         int(max_frames), C.byref(h)))
+        check(self._c("create")(ctx.h, proto.ctypes.data_as(C.c_void_p), proto.size, int(channels), int(hop), phase, int(max_frames),
+                                C.byref(h)))
         self.h = h
+
+    def _c(self, name):
+        return getattr(self._lib, self._prefix + name)
 
     def __del__(self):
         try:
             if self.h and self.ctx.h:
-                self._lib.aeth_chan_destroy(self.h)
+                self._c("destroy")(self.h)
                 self.h = None
         except Exception:
             pass
 
     @property
-    def channels(self): return self._lib.aeth_chan_channels(self.h)
+    def channels(self): return self._c("channels")(self.h)
     @property
-    def ntaps(self): return self._lib.aeth_chan_ntaps(self.h)
+    def ntaps(self): return self._c("ntaps")(self.h)
     @property
-    def hop(self): return self._lib.aeth_chan_hop(self.h)
+    def hop(self): return self._c("hop")(self.h)
     @property
-    def phase(self): return self._lib.aeth_chan_phase(self.h)
+    def phase(self): return self._c("phase")(self.h)
     @property
-    def tile(self): return self._lib.aeth_chan_tile(self.h)
+    def tile(self): return self._c("tile")(self.h)
 
     @property
     def route(self):
         """the inner plan's route (grammar: include/aether_hip.h, aeth_fft_route)"""
-        return self._lib.aeth_chan_route(self.h).decode()
+        return self._c("route")(self.h).decode()
+
+    def _vecs(self, x, hist):
+        if not isinstance(x, DeviceVec):
+            x = self.ctx.vec(x)
+        if hist is not None and not isinstance(hist, DeviceVec):
+            hist = self.ctx.vec(hist)
+        return x, hist
+
+
+class Channelizer(_Bank):
+    """Channelizer(ctx, proto, channels, hop=None, phase="frame"): `proto` holds P * channels real taps, hop defaults to
+    `channels`.  phase="frame": every frame's phase refers to its own first sample (STFT); phase="stream": to the
+    first sample ever fed (pass the global number of a call's first frame as `first_frame`)."""
+    _prefix = "aeth_chan_"
 
     def frames(self, n):
         """frames a call over n input samples makes (n must be a multiple of the hop)"""
         return int(n) // self.hop
 
     def _args(self, x, hist):
-        if not isinstance(x, DeviceVec):
-            x = self.ctx.vec(x)
-        if hist is not None and not isinstance(hist, DeviceVec):
-            hist = self.ctx.vec(hist)
+        x, hist = self._vecs(x, hist)
         if hist is not None and hist.n != self.ntaps - self.hop:
             raise _lib.LengthMismatch(_lib.E_LEN, f"history holds {hist.n} samples, ntaps - hop = {self.ntaps - self.hop}")
         return x, hist, (hist._p() if hist is not None else None)

@@ -10,19 +10,17 @@
 //   general  everything else: a lane owns output q of frame m and reads its P inputs at r = (q - rot) mod M; the
 //            M / D-fold (and, for hop == M with P > 8, the P-fold) overlap is served by L2.
 #include "aeth_internal.h"
-#include "aeth_chan_fold.h"
+#include "aeth_bank.h"
 #include "aeth_fft_plan.h"
 #include "aeth_levels.h"
 
 #include <cmath>
-#include <new>
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr unsigned kMaxP = 64;
+using namespace aeth::bank;
+
 constexpr unsigned kRingMaxP = 8;            // the register ring: P rows + P rows in flight + P taps per column
-constexpr unsigned kGenElems = 4096;         // outputs one workgroup of the general kernel folds: 16 per lane
 
 struct ChanCall {
     const float2 *in, *hist;   // hist: L - D samples in front of in[0], or null (zeros)
@@ -37,15 +35,6 @@ struct ChanCall {
     unsigned stream;           // AETH_CHAN_PHASE_STREAM with D < M
     unsigned g1;               // (first_frame + 1) mod M
 };
-
-template <int CW> struct Row;
-template <> struct Row<1> { typedef float2 T; };
-template <> struct Row<2> { typedef float4 T; };
-
-__device__ __forceinline__ float2 mulw(float2 x, const float *w) { return make_float2(w[0] * x.x, w[0] * x.y); }
-__device__ __forceinline__ float4 mulw(float4 x, const float *w) { return make_float4(w[0] * x.x, w[0] * x.y, w[1] * x.z, w[1] * x.w); }
-__device__ __forceinline__ float2 addv(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float4 addv(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // ---- hop == M, P <= kRingMaxP ----------------------------------------------------------------------------------------
 // Stream row R (M samples) feeds frames R .. R + P - 1 with taps P - 1 .. 0.  Row k of the tile (k = 0 is stream row
@@ -154,55 +143,12 @@ template <int CW, bool NT> ChanKernel ring_kernel(unsigned P)
     }
 }
 
-bool touch_bytes(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
-}
-
 }  // namespace
 
-namespace {
+struct aeth_chan : Bank {};
 
-int ensure_scratch(aeth_chan *c, size_t elems)
-{
-    if (c->scratch_elems >= elems) return AETH_OK;
-    aeth::DeviceGuard dg(c->ctx->device);
-    if (c->scratch) {
-        AETH_HIP(hipStreamSynchronize(aeth::ctx_stream(c->ctx)));
-        AETH_HIP(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_elems = 0;
-    }
-    AETH_HIP(hipMalloc((void **)&c->scratch, elems * sizeof(float2)));
-    c->scratch_elems = elems;
-    return AETH_OK;
-}
-
-}  // namespace
-
-// workgroups of a launch over F frames, at most (the ring kernel with one column per lane)
-size_t aeth::chan_grid_bound(const aeth_chan *c, size_t F)
-{
-    const size_t ntiles = (F + c->tile - 1) / c->tile;
-    if (!c->ring) return ntiles * ((c->M + kGenElems - 1) / kGenElems);
-    size_t lx = 1;
-    while (lx < (size_t)kBlock && lx < c->M) lx *= 2;
-    return ((ntiles + kBlock / lx - 1) / (kBlock / lx)) * ((c->M + lx - 1) / lx);
-}
-
-void aeth::chan_geometry(aeth_chan *c)
-{
-    c->ring = c->D == c->M && c->P <= kRingMaxP;
-    if (c->ring) {
-        // P - 1 halo rows per tile: a sixteenth of the tile at most (P = 2: 1 of 16, P = 8: 7 of 128)
-        c->tile = 16;
-        while (c->tile < 16 * (c->P - 1)) c->tile *= 2;
-    } else {
-        c->tile = c->M <= kGenElems / 2 ? kGenElems / c->M : 1;
-    }
-}
+bool aeth::bank::chan_ring(const Bank &b) { return b.D == b.M && b.P <= kRingMaxP; }
+size_t aeth::bank::chan_tile(const Bank &b) { return chan_ring(b) ? ring_tile(b.P) : gen_tile(b.M); }
 
 namespace {
 
@@ -214,58 +160,56 @@ int check_call(const aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, s
     AETH_REQUIRE(n > 0, AETH_E_LEN, "0 input samples: a call makes at least one frame of hop %zu", c->D);
     AETH_REQUIRE(n % c->D == 0, AETH_E_LEN, "%zu input samples are not a multiple of the hop %zu", n, c->D);
     const size_t F = n / c->D;
-    AETH_REQUIRE(F <= SIZE_MAX / 16 / c->M && n_out == F * c->M, AETH_E_LEN, "output holds %zu elements, %zu frames x %zu channels give %zu",
-                 n_out, F, c->M, F <= SIZE_MAX / 16 / c->M ? F * c->M : (size_t)0);
-    AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(hist), AETH_E_ALIGN, "input or history pointer not 8-byte aligned");
-    AETH_REQUIRE(((uintptr_t)out & (out_elem_bytes - 1)) == 0, AETH_E_ALIGN, "output pointer not %zu-byte aligned", out_elem_bytes);
-    AETH_REQUIRE(!touch_bytes(out, n_out * out_elem_bytes, in, n * sizeof(aeth_cf32)) &&
-                 !touch_bytes(out, n_out * out_elem_bytes, hist, (c->L - c->D) * sizeof(aeth_cf32)), AETH_E_ARG,
-                 "the output range overlaps the input (or its history)");
-    AETH_REQUIRE(aeth::chan_grid_bound(c, F) < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu frames in one call: more than 2^31 workgroups", F);
+    AETH_REQUIRE(frames_fit(*c, F) && n_out == F * c->M, AETH_E_LEN, "output holds %zu elements, %zu frames x %zu channels give %zu",
+                 n_out, F, c->M, frames_fit(*c, F) ? F * c->M : (size_t)0);
     *nframes = F;
-    return AETH_OK;
+    return check_buffers(hist, c->L - c->D, in, n, out, n_out, out_elem_bytes, grid_bound(chan_ring(*c), c->M, ntiles_of(*c, F)), F);
 }
 
 }  // namespace
 
-int aeth::chan_launch_fold(const aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t F, uint64_t first_frame, float2 *out)
+int aeth::bank::chan_launch_fold(const Bank &b, bool stream, const aeth_cf32 *hist, const aeth_cf32 *in, size_t F, uint64_t first_frame,
+                                 float2 *out)
 {
     ChanCall a{};
     a.in = (const float2 *)in;
-    a.hist = c->L > c->D ? (const float2 *)hist : nullptr;
+    a.hist = b.L > b.D ? (const float2 *)hist : nullptr;
     a.out = out;
-    a.w = c->w_dev;
+    a.w = b.taps;
     a.nframes = F;
-    a.M = (unsigned)c->M; a.D = (unsigned)c->D; a.P = (unsigned)c->P;
-    a.tile = (unsigned)c->tile;
+    a.M = (unsigned)b.M; a.D = (unsigned)b.D; a.P = (unsigned)b.P;
+    a.tile = (unsigned)b.tile;
     a.fd_M = aeth::make_fastdiv(a.M);
-    a.stream = c->phase == AETH_CHAN_PHASE_STREAM && c->D < c->M;
-    a.g1 = (unsigned)((first_frame % c->M + 1) % c->M);
-    const size_t ntiles = (F + c->tile - 1) / c->tile;
-    const size_t moved = (F * c->M + F * c->D) * sizeof(float2);
-    const bool nt = aeth::streams_past_cache(moved);
-    ChanKernel k;
-    size_t grid;
-    if (c->ring) {
-        const bool wide = c->M % 2 == 0 && aeth::aligned16(in) && aeth::aligned16(out) && aeth::aligned16(a.hist);
-        const size_t lanes = wide ? c->M / 2 : c->M;                 // lanes along the columns
-        while ((1u << a.lx_log2) < kBlock && ((size_t)1 << a.lx_log2) < lanes) a.lx_log2++;
-        a.ncb = (unsigned)((lanes + (1u << a.lx_log2) - 1) >> a.lx_log2);
-        const size_t ly = kBlock >> a.lx_log2;
-        grid = ((ntiles + ly - 1) / ly) * a.ncb;
-        k = wide ? (nt ? ring_kernel<2, true>(a.P) : ring_kernel<2, false>(a.P)) : (nt ? ring_kernel<1, true>(a.P) : ring_kernel<1, false>(a.P));
-    } else {
-        a.ncb = (unsigned)((c->M + kGenElems - 1) / kGenElems);
-        grid = ntiles * a.ncb;
-        k = nt ? chan_gen_kernel<true> : chan_gen_kernel<false>;
+    a.stream = stream;
+    a.g1 = (unsigned)((first_frame % b.M + 1) % b.M);
+    const size_t ntiles = ntiles_of(b, F);
+    const bool nt = aeth::streams_past_cache((F * b.M + F * b.D) * sizeof(float2));
+    if (!chan_ring(b)) {
+        a.ncb = (unsigned)gen_ncb(b.M);
+        return launch(b, nt ? chan_gen_kernel<true> : chan_gen_kernel<false>, ntiles * a.ncb, a);
     }
-    a.fd_ncb = aeth::make_fastdiv(a.ncb);
-    aeth::DeviceGuard dg(c->ctx->device);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), 0, aeth::ctx_stream(c->ctx), a);
-    AETH_HIP(hipGetLastError());
-    return AETH_OK;
+    const bool wide = b.M % 2 == 0 && aeth::aligned16(in) && aeth::aligned16(out) && aeth::aligned16(a.hist);
+    const RingShape r = ring_shape(wide ? b.M / 2 : b.M, ntiles);       // lanes along the columns
+    a.lx_log2 = r.lx_log2; a.ncb = r.ncb;
+    return launch(b, wide ? (nt ? ring_kernel<2, true>(a.P) : ring_kernel<2, false>(a.P)) : (nt ? ring_kernel<1, true>(a.P) : ring_kernel<1, false>(a.P)),
+                  r.grid, a);
 }
+
+namespace {
+
+int fold(const aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t F, uint64_t first_frame, float2 *out)
+{
+    return chan_launch_fold(*c, c->phase == AETH_CHAN_PHASE_STREAM && c->D < c->M, hist, in, F, first_frame, out);
+}
+
+// fold into the scratch, for the plan to read: `elems` folded samples
+int fold_to_scratch(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t F, uint64_t first_frame, size_t elems)
+{
+    int rc = ensure_elems(*c, elems); if (rc) return rc;
+    return fold(c, hist, in, F, first_frame, (float2 *)c->scratch.p);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -304,45 +248,14 @@ int aeth_chan_prototype(int kind, size_t channels, size_t taps_per_channel, floa
 int aeth_chan_create(aeth_ctx *ctx, const float *proto_host, size_t ntaps, size_t channels, size_t hop, int phase,
                      size_t max_frames, aeth_chan **out)
 {
-    AETH_REQUIRE(out, AETH_E_ARG, "out is null");
-    *out = nullptr;
-    AETH_REQUIRE(ctx, AETH_E_ARG, "ctx is null");
-    AETH_REQUIRE(proto_host, AETH_E_ARG, "prototype is null");
-    AETH_REQUIRE(channels >= 1, AETH_E_ARG, "0 channels");
-    AETH_REQUIRE(ntaps >= 1 && ntaps % channels == 0, AETH_E_ARG, "%zu taps are not a multiple (at least one) of %zu channels", ntaps, channels);
-    AETH_REQUIRE(ntaps / channels <= kMaxP, AETH_E_UNSUPPORTED, "%zu taps per channel: at most %u", ntaps / channels, kMaxP);
-    AETH_REQUIRE(hop >= 1 && hop <= channels, AETH_E_ARG, "hop %zu outside 1 .. %zu channels", hop, channels);
-    AETH_REQUIRE(phase == AETH_CHAN_PHASE_FRAME || phase == AETH_CHAN_PHASE_STREAM, AETH_E_ARG, "bad phase mode %d", phase);
-    aeth_fft *fft = nullptr;
-    int rc = aeth_fft_create(ctx, channels, max_frames, &fft); if (rc) return rc;      // names the refused length
-    aeth_chan *c = new (std::nothrow) aeth_chan();
-    if (!c) { (void)aeth_fft_destroy(fft); return aeth::set_error(AETH_E_NOMEM, "out of host memory"); }
-    c->ctx = ctx; c->fft = fft;
-    c->M = channels; c->L = ntaps; c->P = ntaps / channels; c->D = hop; c->phase = phase;
-    aeth::chan_geometry(c);
-    aeth::DeviceGuard dg(ctx->device);
-    hipError_t e = hipMalloc((void **)&c->w_dev, ntaps * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(c->w_dev, proto_host, ntaps * sizeof(float), hipMemcpyHostToDevice, aeth::ctx_stream(ctx));
-    if (e == hipSuccess) e = hipStreamSynchronize(aeth::ctx_stream(ctx));
-    if (e != hipSuccess) { (void)aeth_chan_destroy(c); return aeth::hip_fail(e, "aeth_chan_create: prototype upload"); }
-    if (max_frames > 0 && max_frames <= SIZE_MAX / 16 / channels) {
-        rc = ensure_scratch(c, max_frames * channels);
-        if (rc) { (void)aeth_chan_destroy(c); return rc; }
-    }
-    *out = c;
-    return AETH_OK;
+    int rc = create_checks(out, ctx, proto_host, ntaps, channels, hop, phase); if (rc) return rc;
+    aeth_chan *c = nullptr;
+    rc = create_planned(ctx, ntaps, channels, hop, phase, max_frames, &c); if (rc) return rc;
+    c->tile = chan_tile(*c);
+    return create_finish(c, proto_host, frames_fit(*c, max_frames) ? max_frames * channels : 0, "aeth_chan_create: prototype upload", out);
 }
 
-int aeth_chan_destroy(aeth_chan *c)
-{
-    if (!c) return AETH_OK;
-    (void)aeth_fft_destroy(c->fft);          // waits for the context's stream
-    aeth::DeviceGuard dg(c->ctx->device);
-    if (c->w_dev) (void)hipFree(c->w_dev);
-    if (c->scratch) (void)hipFree(c->scratch);
-    delete c;
-    return AETH_OK;
-}
+int aeth_chan_destroy(aeth_chan *c) { return destroy(c); }
 
 size_t aeth_chan_channels(const aeth_chan *c) { return c ? c->M : 0; }
 size_t aeth_chan_ntaps(const aeth_chan *c) { return c ? c->L : 0; }
@@ -356,7 +269,7 @@ int aeth_chan_fold(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, siz
 {
     size_t F = 0;
     int rc = check_call(c, hist, in, n, out, n_out, sizeof(aeth_cf32), &F); if (rc) return rc;
-    return aeth::chan_launch_fold(c, hist, in, F, first_frame, (float2 *)out);
+    return fold(c, hist, in, F, first_frame, (float2 *)out);
 }
 
 int aeth_chan_exec(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, uint64_t first_frame, int sign,
@@ -364,11 +277,9 @@ int aeth_chan_exec(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, siz
 {
     size_t F = 0;
     int rc = check_call(c, hist, in, n, out, n_out, sizeof(aeth_cf32), &F); if (rc) return rc;
-    AETH_REQUIRE(sign == AETH_SIGN_REF_FWD || sign == AETH_SIGN_REF_BWD, AETH_E_ARG, "sign must be +1 or -1");
-    AETH_REQUIRE(scale_kind >= AETH_SCALE_NONE && scale_kind <= AETH_SCALE_X, AETH_E_ARG, "bad scale kind %d", scale_kind);
-    rc = ensure_scratch(c, n_out); if (rc) return rc;
-    rc = aeth::chan_launch_fold(c, hist, in, F, first_frame, c->scratch); if (rc) return rc;
-    return aeth_fft_exec(c->fft, (const aeth_cf32 *)c->scratch, n_out, out, F, sign, scale_kind, x);
+    rc = aeth::check_sign_scale(sign, scale_kind); if (rc) return rc;
+    rc = fold_to_scratch(c, hist, in, F, first_frame, n_out); if (rc) return rc;
+    return aeth_fft_exec(c->fft, (const aeth_cf32 *)c->scratch.p, n_out, out, F, sign, scale_kind, x);
 }
 
 int aeth_chan_exec_levels(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, size_t n, uint64_t first_frame, int sign,
@@ -376,12 +287,10 @@ int aeth_chan_exec_levels(aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *
 {
     size_t F = 0;
     int rc = check_call(c, hist, in, n, levels, n_levels, sizeof(float), &F); if (rc) return rc;
-    AETH_REQUIRE(sign == AETH_SIGN_REF_FWD || sign == AETH_SIGN_REF_BWD, AETH_E_ARG, "sign must be +1 or -1");
-    AETH_REQUIRE(scale_kind >= AETH_SCALE_NONE && scale_kind <= AETH_SCALE_X, AETH_E_ARG, "bad scale kind %d", scale_kind);
+    rc = aeth::check_sign_scale(sign, scale_kind); if (rc) return rc;
     AETH_REQUIRE(aeth::level_kind_ok(level_kind), AETH_E_ARG, "bad level kind %d", level_kind);
-    rc = ensure_scratch(c, n_levels); if (rc) return rc;
-    rc = aeth::chan_launch_fold(c, hist, in, F, first_frame, c->scratch); if (rc) return rc;
-    return aeth_fft_exec_levels(c->fft, (const aeth_cf32 *)c->scratch, n_levels, F, sign, scale_kind, x, mirror, level_kind, levels,
+    rc = fold_to_scratch(c, hist, in, F, first_frame, n_levels); if (rc) return rc;
+    return aeth_fft_exec_levels(c->fft, (const aeth_cf32 *)c->scratch.p, n_levels, F, sign, scale_kind, x, mirror, level_kind, levels,
                                 n_levels);
 }
 

@@ -973,9 +973,7 @@ static int ensure_temps(aeth_fft *p, size_t elems, bool host)
 static int check_exec(const aeth_fft *p, int sign, int kind)
 {
     AETH_REQUIRE(p, AETH_E_ARG, "plan is null");
-    AETH_REQUIRE(sign == AETH_SIGN_REF_FWD || sign == AETH_SIGN_REF_BWD, AETH_E_ARG, "sign must be +1 or -1");
-    AETH_REQUIRE(kind >= AETH_SCALE_NONE && kind <= AETH_SCALE_X, AETH_E_ARG, "bad scale kind %d", kind);
-    return AETH_OK;
+    return aeth::check_sign_scale(sign, kind);
 }
 
 int aeth_fft_exec(aeth_fft *p, const aeth_cf32 *in, size_t n_in, aeth_cf32 *out, size_t batch, int sign,
@@ -1022,8 +1020,7 @@ int aeth_fft_exec_levels(aeth_fft *p, const aeth_cf32 *in, size_t n_in, size_t b
     AETH_REQUIRE(in && levels, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned8(in), AETH_E_ALIGN, "pointer not 8-byte aligned");
     AETH_REQUIRE((reinterpret_cast<uintptr_t>(levels) & 3u) == 0, AETH_E_ALIGN, "levels not 4-byte aligned");
-    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + n_in * sizeof(aeth_cf32), b0 = (uintptr_t)levels, b1 = b0 + n_in * sizeof(float);
-    AETH_REQUIRE(a1 <= b0 || b1 <= a0, AETH_E_ARG, "levels overlaps the input");
+    AETH_REQUIRE(!aeth::ranges_touch(in, n_in * sizeof(aeth_cf32), levels, n_in * sizeof(float)), AETH_E_ARG, "levels overlaps the input");
     const float s = aeth_scale_factor(kind, p->len, x);
     if (p->algo == aeth::FFT_ALGO_POW2 && p->len >= 2 && p->len <= 4096) {
         // register-resident transforms: the level is taken of the scaled bin in registers, the spectrum is never written

@@ -171,17 +171,10 @@ int dispatch_fmi(aeth_ctx *ctx, size_t fft_len, const FmiArgs &a, hipStream_t st
 
 bool is_pow2(size_t n) { return n && (n & (n - 1)) == 0; }
 
-// [a, a + na) and [b, b + nb) share a byte?
-bool touch_bytes(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
-}
-// the same in samples
+// [a, a + na) and [b, b + nb) share a sample?
 bool touch(const aeth_cf32 *a, size_t na, const aeth_cf32 *b, size_t nb)
 {
-    return touch_bytes(a, na * sizeof(aeth_cf32), b, nb * sizeof(aeth_cf32));
+    return aeth::ranges_touch(a, na * sizeof(aeth_cf32), b, nb * sizeof(aeth_cf32));
 }
 
 // ---- aeth_corr_search: from the waves' records to the per-block records and the best of the stream -------------------
@@ -564,8 +557,8 @@ int aeth_corr_exec_levels(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *
     AETH_REQUIRE(in && levels, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(hist), AETH_E_ALIGN, "%s", kMsgFirAlign);
     AETH_REQUIRE((reinterpret_cast<uintptr_t>(levels) & 3u) == 0, AETH_E_ALIGN, "levels not 4-byte aligned");
-    AETH_REQUIRE(!touch_bytes(levels, n * sizeof(float), in, n * sizeof(aeth_cf32)) &&
-                 !touch_bytes(levels, n * sizeof(float), hist, (f->ntaps - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
+    AETH_REQUIRE(!aeth::ranges_touch(levels, n * sizeof(float), in, n * sizeof(aeth_cf32)) &&
+                 !aeth::ranges_touch(levels, n * sizeof(float), hist, (f->ntaps - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
                  "levels overlaps the input (or its history)");
     AETH_REQUIRE(fused_store_len(f->fft_len), AETH_E_UNSUPPORTED,
                  "level store: fft_len %zu (one-block-per-workgroup lengths 1024 .. 4096 only)", f->fft_len);
@@ -586,8 +579,8 @@ int aeth_corr_search(aeth_corr *c, const aeth_cf32 *hist, const aeth_cf32 *in, s
                  nblocks, f->hop);
     AETH_REQUIRE(in, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(hist) && aeth::aligned8(peaks), AETH_E_ALIGN, "%s", kMsgFirAlign);
-    AETH_REQUIRE(!touch_bytes(peaks, nblocks * sizeof(aeth_corr_peak), in, n * sizeof(aeth_cf32)) &&
-                 !touch_bytes(peaks, nblocks * sizeof(aeth_corr_peak), hist, (f->ntaps - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
+    AETH_REQUIRE(!aeth::ranges_touch(peaks, nblocks * sizeof(aeth_corr_peak), in, n * sizeof(aeth_cf32)) &&
+                 !aeth::ranges_touch(peaks, nblocks * sizeof(aeth_corr_peak), hist, (f->ntaps - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
                  "peaks overlaps the input (or its history)");
     AETH_REQUIRE(fused_store_len(f->fft_len), AETH_E_UNSUPPORTED,
                  "peak search: fft_len %zu (one-block-per-workgroup lengths 1024 .. 4096 only)", f->fft_len);

@@ -71,10 +71,11 @@ inline hipStream_t ctx_stream(const aeth_ctx *ctx) { return ctx_stream(const_cas
 hipStream_t ctx_fir_lane(aeth_ctx *ctx, uintptr_t in_lo, uintptr_t in_hi, uintptr_t out_lo, uintptr_t out_hi);
 
 // Ensure `s` holds >= bytes of device memory: nothing happens when it already does; else it is replaced by a buffer of
-// bytes + bytes/4.  The context's stream is waited for before the old buffer is freed.  (The staging slots used to be
+// bytes + bytes/4 (`slack`: the context's own buffers) or of exactly bytes (the filter banks' frames, aeth_bank.h).  The
+// context's stream is waited for before the old buffer is freed.  (The staging slots used to be
 // freed without that wait: hipFree waits for the device itself and the host-slice calls are synchronous, so the
 // explicit wait changes nothing observable there.)
-int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes);
+int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes, bool slack = true);
 // frees it; on a failed free the buffer stays recorded and the HIP error is returned (aeth_ctx_trim reports it,
 // aeth_ctx_destroy does not)
 hipError_t scratch_release(DevScratch &s);
@@ -119,6 +120,13 @@ constexpr int lab_int(const char *, int dflt) { return dflt; }
 
 inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// [a, a + na) and [b, b + nb) share a byte?  (never for a null pointer or an empty range)
+inline bool ranges_touch(const void *a, size_t na, const void *b, size_t nb)
+{
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
+}
 
 // n / d for 32-bit n by multiply-high and shifts (Granlund-Montgomery round-up form):
 // index arithmetic of store-bound kernels must not cost more than their stores.
@@ -199,6 +207,16 @@ struct DeviceGuard {
     do {                                                            \
         if (!(cond)) return aeth::set_error((code), __VA_ARGS__);   \
     } while (0)
+
+namespace aeth {
+// what every transforming call asks of its sign and Scale kind
+inline int check_sign_scale(int sign, int kind)
+{
+    AETH_REQUIRE(sign == AETH_SIGN_REF_FWD || sign == AETH_SIGN_REF_BWD, AETH_E_ARG, "sign must be +1 or -1");
+    AETH_REQUIRE(kind >= AETH_SCALE_NONE && kind <= AETH_SCALE_X, AETH_E_ARG, "bad scale kind %d", kind);
+    return AETH_OK;
+}
+}  // namespace aeth
 
 // message texts of the reference's panics (kept verbatim for the binding)
 #define AETH_MSG_VEC_LEN "Vectors must have same length"            /* src/vecops.rs:100-104 */

@@ -106,7 +106,7 @@ hipStream_t ctx_fir_lane(aeth_ctx *ctx, uintptr_t in_lo, uintptr_t in_hi, uintpt
     return s;
 }
 
-int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes)
+int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes, bool slack)
 {
     if (s.bytes >= bytes) return AETH_OK;
     DeviceGuard dev_guard(ctx->device);
@@ -114,7 +114,7 @@ int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes)
         AETH_HIP(hipStreamSynchronize(ctx_stream(ctx)));
         AETH_HIP(scratch_release(s));
     }
-    const size_t want = bytes + bytes / 4;
+    const size_t want = slack ? bytes + bytes / 4 : bytes;
     AETH_HIP(hipMalloc(&s.p, want));
     s.bytes = want;
     return AETH_OK;

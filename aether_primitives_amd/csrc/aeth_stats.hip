@@ -261,8 +261,7 @@ int aeth_vec_levels(aeth_ctx *ctx, const aeth_cf32 *x_dev, size_t n, int kind, f
     AETH_REQUIRE(x_dev && levels_dev, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned8(x_dev), AETH_E_ALIGN, "x not 8-byte aligned");
     AETH_REQUIRE((reinterpret_cast<uintptr_t>(levels_dev) & 3u) == 0, AETH_E_ALIGN, "levels not 4-byte aligned");
-    const uintptr_t a0 = (uintptr_t)x_dev, a1 = a0 + n * sizeof(aeth_cf32), b0 = (uintptr_t)levels_dev, b1 = b0 + n * sizeof(float);
-    AETH_REQUIRE(a1 <= b0 || b1 <= a0, AETH_E_ARG, "levels overlaps x");
+    AETH_REQUIRE(!aeth::ranges_touch(x_dev, n * sizeof(aeth_cf32), levels_dev, n * sizeof(float)), AETH_E_ARG, "levels overlaps x");
     AETH_REQUIRE((n + 1) / 2 / kBlock < 0x7fffffffu, AETH_E_UNSUPPORTED, "%zu samples", n);
     aeth::DeviceGuard dev_guard(ctx->device);
     const float2 *x = reinterpret_cast<const float2 *>(x_dev);

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .chan import PHASE_FRAME, _PHASES
+from .chan import _Bank
 from .context import DeviceVec
 from .fft import SIGN_REF_BWD, Scale
 
@@ -23,60 +23,23 @@ def dual_window(w, hop):
     return out[:w.size]
 
 
-class Synthesizer:
+class Synthesizer(_Bank):
     """Synthesizer(ctx, proto, channels, hop=None, phase="frame"): `proto` holds P * channels real taps, hop defaults to
     `channels`; phase as for `Channelizer` (pass the global number of a call's first frame as `first_frame`).  A call
     reads `history` frames in front of its own: the previous call's last ones, or zeros."""
-
-    def __init__(self, ctx, proto, channels, hop=None, phase=PHASE_FRAME, max_frames=0):
-        self.ctx = ctx
-        self._lib = _lib.load()
-        proto = np.ascontiguousarray(proto, dtype=np.float32).reshape(-1)
-        hop = channels if hop is None else hop
-        phase = _PHASES[phase.lower()] if isinstance(phase, str) else int(phase)
-        h = C.c_void_p()
-        check(self._lib.aeth_synth_create(ctx.h, proto.ctypes.data_as(C.c_void_p), proto.size, int(channels), int(hop), phase,
-                                          int(max_frames), C.byref(h)))
-        self.h = h
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self._lib.aeth_synth_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    @property
-    def channels(self): return self._lib.aeth_synth_channels(self.h)
-    @property
-    def ntaps(self): return self._lib.aeth_synth_ntaps(self.h)
-    @property
-    def hop(self): return self._lib.aeth_synth_hop(self.h)
-    @property
-    def phase(self): return self._lib.aeth_synth_phase(self.h)
-    @property
-    def tile(self): return self._lib.aeth_synth_tile(self.h)
+    _prefix = "aeth_synth_"
 
     @property
     def history(self):
         """frames in front of a call's first that reach into its output: ceil(ntaps / hop) - 1"""
         return self._lib.aeth_synth_history(self.h)
 
-    @property
-    def route(self):
-        """the inner plan's route (grammar: include/aether_hip.h, aeth_fft_route)"""
-        return self._lib.aeth_synth_route(self.h).decode()
-
     def samples(self, n_in):
         """output samples of a call over n_in input samples (n_in must be a multiple of `channels`)"""
         return int(n_in) // self.channels * self.hop
 
     def _args(self, v, hist):
-        if not isinstance(v, DeviceVec):
-            v = self.ctx.vec(v)
-        if hist is not None and not isinstance(hist, DeviceVec):
-            hist = self.ctx.vec(hist)
+        v, hist = self._vecs(v, hist)
         if hist is not None and hist.n != self.history * self.channels:
             raise _lib.LengthMismatch(_lib.E_LEN, f"history holds {hist.n} samples, {self.history} frames x {self.channels} "
                                       f"channels = {self.history * self.channels}")

@@ -13,7 +13,8 @@ in the translation unit changes has been normalised away: comments, and the func
 (.LBB94_7 -> .LBB_7).  A build whose only remaining differences are scalar loads of the HIDDEN kernel arguments (grid
 size and the like, which sit behind the explicit ones), each moved by exactly the growth of FmiArgs, counts as
 identical: that is the kernarg size and nothing else.  Prints one line per build that differs or whose name contains
-one of the substrings, with the kernel descriptors' register counts, LDS and kernarg sizes, and a summary line."""
+one of the substrings, with the kernel descriptors' register counts, LDS and kernarg sizes, and a summary line.  A
+function of the family without a kernel descriptor in either file ends the run with an error: every build counts."""
 import hashlib
 import re
 import sys
@@ -38,14 +39,18 @@ def funcs(path):
 
 
 def meta(path):
-    out, cur = {}, {}
+    """{kernel: its descriptor fields} from amdhsa.kernels: a record opens with "  - .key:", its own keys are indented by
+    four blanks (deeper ones belong to .args), and .name comes in the middle of them"""
+    out, cur = {}, None
     keys = "name|vgpr_count|sgpr_count|vgpr_spill_count|private_segment_fixed_size|kernarg_segment_size|group_segment_fixed_size"
     for line in open(path):
-        m = re.match(r"\s+\.(" + keys + r"):\s+(\S+)", line)
-        if not m:
+        if line.startswith("  - ."):
+            cur = {}
+        m = re.match(r"(?:  - |    )\.(" + keys + r"):\s+(\S+)", line)
+        if not m or cur is None:
             continue
         if m.group(1) == "name":
-            cur = out.setdefault(m.group(2), {})
+            out[m.group(2)] = cur
         else:
             cur[m.group(1)] = int(m.group(2))
     return out
@@ -73,7 +78,7 @@ def main():
             print("ONLY IN OLD", k)
             continue
         if "kernarg_segment_size" not in ma.get(k, {}) or "kernarg_segment_size" not in mb.get(k, {}):
-            continue                                                # a label, not a kernel
+            sys.exit(f"{k}: in the family, without a kernel descriptor in {old if 'kernarg_segment_size' not in ma.get(k, {}) else new}")
         grow = mb[k]["kernarg_segment_size"] - ma[k]["kernarg_segment_size"]
         eq = len(a[k]) == len(b[k]) and all(x == y or hidden_arg_moved(x, y, ma[k]["kernarg_segment_size"] - 256, grow)
                                             for x, y in zip(a[k], b[k]))
