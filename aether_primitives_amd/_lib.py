@@ -40,6 +40,7 @@ PROTOTYPES = {
     "aeth_ctx_sync": (i32, [vp]),
     "aeth_ctx_set_overlap": (i32, [vp, i32]),
     "aeth_ctx_overlap": (i32, [vp]),
+    "aeth_ctx_lane_counts": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
     "aeth_ctx_stream": (vp, [vp]),
     "aeth_ctx_device": (i32, [vp]),
     "aeth_dev_alloc": (i32, [vp, sz, pvp]),

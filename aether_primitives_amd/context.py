@@ -89,6 +89,13 @@ class Context:
     def overlap(self):
         return bool(self._lib.aeth_ctx_overlap(self.h))
 
+    def lane_counts(self):
+        """(packets, joins) the overlap lane has spent on ordering so far: event packets in front of its launches, and
+        chains it ended by joining the two queues."""
+        p, j = C.c_uint64(), C.c_uint64()
+        check(self._lib.aeth_ctx_lane_counts(self.h, C.byref(p), C.byref(j)))
+        return p.value, j.value
+
     @property
     def stream(self):
         """hipStream_t of the context for interop.  SIDE EFFECT: handing the stream out parks the overlap lane (every

@@ -379,13 +379,13 @@ int aeth_fft_mul_ifft_demod(aeth_fft *plan, const aeth_cf32 *frames, size_t n_to
     // demod_naive scans 2 * bps candidates (modulation.rs:135): all four for QPSK
     a.demod_sep = bps == 2 && tb[0].re == tb[2].re && tb[1].re == tb[3].re && tb[0].im == tb[1].im && tb[2].im == tb[3].im;
     // out of place (frames are only read), so consecutive calls on disjoint buffers can run on the context's two
-    // queues like consecutive aeth_fir_exec calls do (aeth_ctx_set_overlap): the drain of one beside the fill of the next
-    // (a reference signal that the previous chained launch may still be writing keeps this call on the in-order stream)
-    aeth_ctx *cx = plan->ctx;
-    const bool sig_busy = cx->chain_last >= 0 && (uintptr_t)sig < cx->last_out[1] && cx->last_out[0] < (uintptr_t)(sig + n_sig);
-    hipStream_t lane = sig_busy ? aeth::ctx_stream(cx)
-                                : aeth::ctx_fir_lane(cx, (uintptr_t)frames, (uintptr_t)(frames + n_total), (uintptr_t)bits_out,
-                                                     (uintptr_t)(bits_out + nbits_out));
+    // queues like consecutive aeth_fir_exec calls do (aeth_ctx_set_overlap): the drain of one beside the fill of the next.
+    // The reference signal is read by every workgroup until the launch ends, so it is an input like the frames.
+    aeth::lanes::Access acc;
+    acc.in[0] = aeth::lanes::range_of(frames, n_total * sizeof(aeth_cf32));
+    acc.in[1] = aeth::lanes::range_of(sig, n_sig * sizeof(aeth_cf32));
+    acc.out = aeth::lanes::range_of(bits_out, nbits_out);
+    hipStream_t lane = aeth::ctx_fir_lane(plan->ctx, acc);
     return dispatch_fmi(plan->ctx, plan->len, a, lane);
 }
 
@@ -449,8 +449,10 @@ int aeth_fir_exec(aeth_fir *f, const aeth_cf32 *hist, const aeth_cf32 *in, size_
     if (int rc = fir_check(f, hist, in, n, out, n)) return rc;
     // independent consecutive launches alternate between the context's two queues (aeth_ctx_set_overlap); a history
     // buffer is usually the tail of something just written, so such calls stay on the in-order stream
-    hipStream_t lane = hist ? aeth::ctx_stream(f->ctx)
-                            : aeth::ctx_fir_lane(f->ctx, (uintptr_t)in, (uintptr_t)(in + n), (uintptr_t)out, (uintptr_t)(out + n));
+    aeth::lanes::Access acc;
+    acc.in[0] = aeth::lanes::range_of(in, n * sizeof(aeth_cf32));
+    acc.out = aeth::lanes::range_of(out, n * sizeof(aeth_cf32));
+    hipStream_t lane = hist ? aeth::ctx_stream(f->ctx) : aeth::ctx_fir_lane(f->ctx, acc);
     return aeth::fir_exec_on(f, lane, hist, in, n, out);
 }
 

@@ -10,6 +10,7 @@
 #include <cstdio>
 
 #include "../../include/aether_hip.h"
+#include "aeth_lane_hazards.h"
 
 namespace aeth {
 struct PipeState;
@@ -25,14 +26,15 @@ struct aeth_ctx {
     hipStream_t stream_main = nullptr;   // use aeth::ctx_stream(ctx): it orders the caller behind the overlap lane
     bool owns_stream = false;
     int num_cus = 256;
-    // Overlap lane (aeth_ctx_set_overlap): a second HIP queue.  Consecutive fused-FIR launches whose buffers do not
-    // touch each other alternate between the two queues, so that the drain of one launch (its last round only
-    // stores) runs beside the fill of the next (its first round only loads).  Every launch is ordered behind
-    // everything except its immediate predecessor; any other call on the context joins the lane first, so
+    // Overlap lane (aeth_ctx_set_overlap): a second HIP queue.  Consecutive fused-FIR launches alternate between the
+    // two queues, so that the drain of one launch (its last round only stores) runs beside the fill of the next (its
+    // first round only loads).  A chain starts on the main stream behind everything enqueued before it; each later
+    // launch goes where no buffer hazard is left open (ctx_fir_lane: `hazards` holds the ranges of both lanes since
+    // the last join), with no event packet in front of it.  Any other call on the context joins the lane first, so
     // results are those of one in-order stream.
     hipStream_t stream_aux = nullptr;
-    hipEvent_t ev_pre[2] = {nullptr, nullptr};   // [lane] recorded on that lane right before its latest FIR launch
-    bool ev_pre_empty[2] = {false, false};       // ... unless that launch started on an idle context: nothing was in front of it
+    hipEvent_t ev_head = nullptr;  // recorded on the main stream in front of the head of a chain, unless the context was idle
+    bool aux_behind_head = false;  // ... and the aux lane has not waited for it yet: its first launch of the chain does
     hipEvent_t ev_aux_done = nullptr;
     bool overlap = false;          // feature switch (off for borrowed streams)
     bool stream_shared = false;    // aeth_ctx_stream() handed the main stream to code this library does not see: the
@@ -40,7 +42,9 @@ struct aeth_ctx {
     bool aux_pending = false;      // the aux lane holds work the main stream is not yet ordered behind
     int chain_last = -1;           // lane of the latest FIR launch while nothing else has been enqueued since; else -1
     bool last_chained = false;     // the latest ctx_fir_lane call put its launch beside its predecessor
-    uintptr_t last_in[2] = {0, 0}, last_out[2] = {0, 0};   // [lo, hi) byte ranges of that launch
+    aeth::lanes::Tracker hazards;  // what the launches of the chain read and write, per lane; reset with chain_last
+    uint64_t lane_packets = 0;     // event-wait / event-record packets ctx_fir_lane has put in front of launches
+    uint64_t lane_joins = 0;       // chains ctx_fir_lane ended itself: a hazard on both lanes, or a full tracker
     unsigned since_sync = 0;       // stream hand-outs (= launches, roughly) since the last aeth_ctx_sync: a short wait blocks, a long one polls
     // host pipeline (aeth_fir_stream_host): stage streams, device slots, events, pinned staging pool, copy threads --
     // created on its first run and kept (aeth_host.h)
@@ -66,9 +70,18 @@ int hip_fail(hipError_t e, const char *what);
 // what the aux lane still holds) and ends the chain.
 hipStream_t ctx_stream(aeth_ctx *ctx);
 inline hipStream_t ctx_stream(const aeth_ctx *ctx) { return ctx_stream(const_cast<aeth_ctx *>(ctx)); }
-// Stream for a fused-FIR launch reading [in_lo, in_hi) and writing [out_lo, out_hi): the other lane when the
-// previous call on this context was such a launch and the buffers are disjoint, else the main stream.
-hipStream_t ctx_fir_lane(aeth_ctx *ctx, uintptr_t in_lo, uintptr_t in_hi, uintptr_t out_lo, uintptr_t out_hi);
+// Stream for a fused-FIR launch that reads a.in[] and writes a.out (EVERY buffer the caller owns and the kernel
+// touches).  While the previous call on this context was such a launch: the lane beside it when `a` has no hazard
+// with anything on the predecessor's lane, the predecessor's own lane (in order behind it) when the hazards are all
+// there, else the main stream behind a join.
+hipStream_t ctx_fir_lane(aeth_ctx *ctx, const lanes::Access &a);
+// no launch of the lane is the context's latest call any more: the next ctx_fir_lane starts a chain
+inline void ctx_chain_end(aeth_ctx *ctx)
+{
+    ctx->chain_last = -1;
+    ctx->last_chained = false;
+    ctx->hazards.reset();
+}
 
 // Ensure `s` holds >= bytes of device memory: nothing happens when it already does; else it is replaced by a buffer of
 // bytes + bytes/4 (`slack`: the context's own buffers) or of exactly bytes (the filter banks' frames, aeth_bank.h).  The

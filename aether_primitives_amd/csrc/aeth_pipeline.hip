@@ -103,8 +103,8 @@ struct StageOp {
 // pipeline has drained the context's own stream before its first chunk, so nothing else can be enqueued meanwhile.
 struct StreamSwap {
     aeth_ctx *c; hipStream_t saved; bool overlap;
-    StreamSwap(aeth_ctx *ctx, hipStream_t s) : c(ctx), saved(ctx->stream_main), overlap(ctx->overlap) { c->stream_main = s; c->overlap = false; c->chain_last = -1; }
-    ~StreamSwap() { c->stream_main = saved; c->overlap = overlap; c->chain_last = -1; }
+    StreamSwap(aeth_ctx *ctx, hipStream_t s) : c(ctx), saved(ctx->stream_main), overlap(ctx->overlap) { c->stream_main = s; c->overlap = false; aeth::ctx_chain_end(c); }
+    ~StreamSwap() { c->stream_main = saved; c->overlap = overlap; aeth::ctx_chain_end(c); }
 };
 
 // streams, events, device slots of `din_bytes` / `dout_bytes`, grown (never shrunk; aeth_ctx_trim releases) between calls

@@ -48,61 +48,56 @@ hipStream_t ctx_stream(aeth_ctx *ctx)
         else (void)hipStreamSynchronize(ctx->stream_aux);
         ctx->aux_pending = false;
     }
-    ctx->chain_last = -1;
-    ctx->last_chained = false;
+    ctx_chain_end(ctx);
     ctx->since_sync++;
     return ctx->stream_main;
 }
 
-static inline bool ranges_touch(uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi)
-{
-    return a_lo < b_hi && b_lo < a_hi;
-}
-
-hipStream_t ctx_fir_lane(aeth_ctx *ctx, uintptr_t in_lo, uintptr_t in_hi, uintptr_t out_lo, uintptr_t out_hi)
+hipStream_t ctx_fir_lane(aeth_ctx *ctx, const lanes::Access &a)
 {
     if (!ctx->overlap || ctx->stream_shared) return ctx_stream(ctx);
     const int prev = ctx->chain_last;
-    bool chained = prev >= 0;
-    if (chained) {
-        // the only launch this one is NOT ordered behind is its immediate predecessor: their buffers must be disjoint
-        const uintptr_t *pi = ctx->last_in, *po = ctx->last_out;
-        if (ranges_touch(in_lo, in_hi, po[0], po[1]) || ranges_touch(out_lo, out_hi, pi[0], pi[1]) ||
-            ranges_touch(out_lo, out_hi, po[0], po[1]))
-            chained = false;
-    }
-    int lane = 0;
-    hipStream_t s;
-    // nothing has been handed a stream since the last aeth_ctx_sync: both queues are idle and this launch has no history
-    const bool idle = ctx->since_sync == 0 && !ctx->aux_pending;
-    if (!chained) {
-        s = ctx_stream(ctx);                    // joins; everything enqueued so far is in front of this launch
-    } else {
-        lane = 1 - prev;
-        s = lane ? ctx->stream_aux : ctx->stream_main;
-        // behind everything the other lane held BEFORE its latest launch (which itself runs beside this one) -- if it
-        // held anything: a launch that started on an idle context has nothing in front of it, and no wait packet then
-        // sits in front of this kernel
-        if (!ctx->ev_pre_empty[prev] && hipStreamWaitEvent(s, ctx->ev_pre[prev], 0) != hipSuccess) { s = ctx_stream(ctx); lane = 0; }
-    }
-    if (!chained && idle) {
-        // the head of a chain on an idle context: no history to mark, so no event-record packet in front of the kernel
-        // (measured: a K = 1 region 68.1 us with the packet, 65.1 us without, tools/k20_lab.py)
-        ctx->ev_pre_empty[lane] = true;
-    } else {
-        ctx->ev_pre_empty[lane] = false;
-        if (hipEventRecord(ctx->ev_pre[lane], s) != hipSuccess) {   // this lane's history in front of the launch
-            s = ctx_stream(ctx); lane = 0;
-            ctx->chain_last = -1;                   // no chain without the event
-            return s;
+    if (prev >= 0) {
+        // Both lanes are in-order queues, so a launch is ordered behind every record of the lane it goes to.  Beside
+        // its predecessor when nothing on the predecessor's lane touches its buffers; behind it, on that very queue,
+        // when the hazards are all there (a dependent chain, or a rotation that brings a buffer back on the other
+        // lane): either way no packet sits in front of the kernel.
+        int lane = -1;
+        if (!ctx->hazards.hazards(prev, a)) lane = 1 - prev;
+        else if (!ctx->hazards.hazards(1 - prev, a)) lane = prev;
+        if (lane >= 0 && ctx->hazards.note(lane, a)) {
+            bool ok = true;
+            if (lane == 1 && ctx->aux_behind_head) {
+                // the aux lane's first launch of the chain: once behind everything enqueued before the head
+                ctx->lane_packets++;
+                ok = hipStreamWaitEvent(ctx->stream_aux, ctx->ev_head, 0) == hipSuccess;
+                if (ok) ctx->aux_behind_head = false;
+            }
+            if (ok) {
+                if (lane == 1) ctx->aux_pending = true;
+                ctx->since_sync++;
+                ctx->last_chained = lane != prev;
+                ctx->chain_last = lane;
+                return lane ? ctx->stream_aux : ctx->stream_main;
+            }
         }
+        ctx->lane_joins++;                      // hazards on both lanes, a full tracker, or no wait: the chain ends
     }
-    if (lane == 1) ctx->aux_pending = true;
+    // The head of a chain: on the main stream, behind the join and so behind everything enqueued so far.
+    // Nothing has been handed a stream since the last aeth_ctx_sync: both queues are idle, this launch has no history,
+    // and no event-record packet sits in front of the kernel (measured: a K = 1 region 68.1 us with the packet, 65.1 us
+    // without, tools/k20_lab.py)
+    const bool idle = ctx->since_sync == 0 && !ctx->aux_pending;
+    hipStream_t s = ctx_stream(ctx);
+    ctx->aux_behind_head = false;
+    if (!idle) {
+        ctx->lane_packets++;
+        if (hipEventRecord(ctx->ev_head, s) != hipSuccess) return s;     // no chain without the event
+        ctx->aux_behind_head = true;
+    }
+    (void)ctx->hazards.note(0, a);              // the tracker is empty here
     ctx->since_sync++;
-    ctx->last_chained = chained;
-    ctx->chain_last = lane;
-    ctx->last_in[0] = in_lo; ctx->last_in[1] = in_hi;
-    ctx->last_out[0] = out_lo; ctx->last_out[1] = out_hi;
+    ctx->chain_last = 0;
     return s;
 }
 
@@ -220,9 +215,9 @@ static int ctx_make(int device, hipStream_t borrowed, bool borrow, aeth_ctx **ou
 static void overlap_release(aeth_ctx *c)
 {
     if (c->stream_aux) { (void)hipStreamSynchronize(c->stream_aux); (void)hipStreamDestroy(c->stream_aux); c->stream_aux = nullptr; }
-    for (int i = 0; i < 2; i++) if (c->ev_pre[i]) { (void)hipEventDestroy(c->ev_pre[i]); c->ev_pre[i] = nullptr; }
+    if (c->ev_head) { (void)hipEventDestroy(c->ev_head); c->ev_head = nullptr; }
     if (c->ev_aux_done) { (void)hipEventDestroy(c->ev_aux_done); c->ev_aux_done = nullptr; }
-    c->overlap = false; c->aux_pending = false; c->chain_last = -1;
+    c->overlap = false; c->aux_pending = false; c->aux_behind_head = false; aeth::ctx_chain_end(c);
 }
 
 int aeth_ctx_set_overlap(aeth_ctx *ctx, int enable)
@@ -239,7 +234,7 @@ int aeth_ctx_set_overlap(aeth_ctx *ctx, int enable)
     ctx->stream_shared = false;                  // (re-)armed by the caller: whoever holds the stream pointer has been told
     if (ctx->overlap) return AETH_OK;
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream_aux, hipStreamNonBlocking);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ctx->ev_pre[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_head, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_aux_done, hipEventDisableTiming);
     if (e != hipSuccess) { overlap_release(ctx); return aeth::hip_fail(e, "overlap lane set-up"); }
     ctx->overlap = true;
@@ -248,6 +243,14 @@ int aeth_ctx_set_overlap(aeth_ctx *ctx, int enable)
 
 /* 1 only while the lane is in USE: handing the stream out (aeth_ctx_stream) parks it until it is re-armed */
 int aeth_ctx_overlap(const aeth_ctx *ctx) { return ctx && ctx->overlap && !ctx->stream_shared ? 1 : 0; }
+
+int aeth_ctx_lane_counts(const aeth_ctx *ctx, uint64_t *packets, uint64_t *joins)
+{
+    AETH_REQUIRE(ctx, AETH_E_ARG, "ctx is null");
+    if (packets) *packets = ctx->lane_packets;
+    if (joins) *joins = ctx->lane_joins;
+    return AETH_OK;
+}
 
 int aeth_ctx_create(int device, aeth_ctx **out) { return ctx_make(device, nullptr, false, out); }
 
@@ -312,8 +315,7 @@ int aeth_ctx_sync(aeth_ctx *ctx)
     for (int i = nw - 1; i >= 0; i--)
         if (!done[i]) AETH_HIP(hipStreamSynchronize(waits[i]));
     ctx->aux_pending = false;
-    ctx->chain_last = -1;
-    ctx->last_chained = false;
+    aeth::ctx_chain_end(ctx);
     return AETH_OK;
 }
 

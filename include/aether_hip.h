@@ -103,12 +103,20 @@ AETH_API int aeth_ctx_create_on_stream(int device, void *hip_stream, aeth_ctx **
 AETH_API int aeth_ctx_destroy(aeth_ctx *ctx);
 AETH_API int aeth_ctx_sync(aeth_ctx *ctx);
 /* Overlap lane (no reference counterpart: the reference is synchronous; this is the device analogue of keeping
- * two stages of src/pipeline.rs:52-137 busy).  When enabled, consecutive aeth_fir_exec calls whose buffers do not
- * touch each other alternate between two HIP queues of the context, so that the end of one launch overlaps the
- * start of the next; every other call (and aeth_ctx_sync / aeth_event_record) is ordered behind both queues, so
+ * two stages of src/pipeline.rs:52-137 busy).  When enabled, consecutive aeth_fir_exec (and aeth_fft_mul_ifft_demod)
+ * calls alternate between two HIP queues of the context, so that the end of one launch overlaps the start of the
+ * next.  The ordering guarantee: such a launch is ordered behind every earlier launch whose buffers it touches --
+ * it reads what that one writes, or writes what that one reads or writes, in any byte -- and behind everything
+ * enqueued on the context before the first of these launches; launches that share no buffer may run in either order
+ * or side by side.  Every other call (and aeth_ctx_sync / aeth_event_record) is ordered behind both queues, so
  * results are those of one in-order stream.  Off by default; refused for contexts on a borrowed stream. */
 AETH_API int aeth_ctx_set_overlap(aeth_ctx *ctx, int enable);
 AETH_API int aeth_ctx_overlap(const aeth_ctx *ctx);   /* 1 if enabled AND in use (0 while aeth_ctx_stream has parked it) */
+/* What the lane has spent on ordering since the context was created (either pointer may be null): event-wait and
+ * event-record packets put in front of its launches, and chains it ended with a join of the two queues because a
+ * launch touched buffers of launches on both (or the host's record of them was full).  A chain of independent
+ * launches over a rotating buffer set costs at most two packets at its start (none on an idle context) and none after. */
+AETH_API int aeth_ctx_lane_counts(const aeth_ctx *ctx, uint64_t *packets, uint64_t *joins);
 /* hipStream_t of the context, for interop (torch ExternalStream, the caller's own copies and kernels).  Handing it out
  * parks the overlap lane: every later launch stays on this stream, so work the caller enqueues on it is ordered behind
  * the library's, until the caller re-arms the lane with aeth_ctx_set_overlap(ctx, 1). */

@@ -93,6 +93,7 @@ extern "C" {
     pub fn aeth_ctx_sync(ctx: *mut aeth_ctx) -> c_int;
     pub fn aeth_ctx_set_overlap(ctx: *mut aeth_ctx, enable: c_int) -> c_int;
     pub fn aeth_ctx_overlap(ctx: *const aeth_ctx) -> c_int;
+    pub fn aeth_ctx_lane_counts(ctx: *const aeth_ctx, packets: *mut u64, joins: *mut u64) -> c_int;
     pub fn aeth_dev_alloc(ctx: *mut aeth_ctx, bytes: usize, dptr: *mut *mut c_void) -> c_int;
     pub fn aeth_dev_free(ctx: *mut aeth_ctx, dptr: *mut c_void) -> c_int;
     pub fn aeth_upload(ctx: *mut aeth_ctx, dst: *mut c_void, src: *const c_void, bytes: usize) -> c_int;

@@ -39,6 +39,10 @@ configs = [
     ("2q first12 ch11", True, 12, 11, False),
     ("2q first12 ch13", True, 12, 13, False),
     ("2q first14 ch12", True, 14, 12, False),
+    ("2q first16 ch11", True, 16, 11, False),
+    ("2q first16 ch13", True, 16, 13, False),
+    ("2q first16 ch14", True, 16, 14, False),
+    ("2q first16 ch15", True, 16, 15, False),
     ("1q", False, 16, 16, False),
     # oversubscribed grids: more workgroups than fit at once -- the ones without a slot start as their predecessor's
     # finish, so the LAST launch of a chain can fill the whole machine while it drains
