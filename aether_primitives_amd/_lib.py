@@ -186,6 +186,17 @@ PROTOTYPES = {
     "aeth_synth_unfold": (i32, [vp, vp, vp, sz, u64, vp, sz]),
     "aeth_synth_exec": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, vp, sz]),
     "aeth_synth_dual_window": (i32, [vp, sz, sz, vp]),
+    "aeth_resamp_create": (i32, [vp, vp, sz, sz, sz, pvp]),
+    "aeth_resamp_destroy": (i32, [vp]),
+    "aeth_resamp_up": (sz, [vp]),
+    "aeth_resamp_down": (sz, [vp]),
+    "aeth_resamp_ntaps": (sz, [vp]),
+    "aeth_resamp_history": (sz, [vp]),
+    "aeth_resamp_tile": (sz, [vp]),
+    "aeth_resamp_route": (C.c_char_p, [vp]),
+    "aeth_resamp_out_count": (sz, [vp, sz]),
+    "aeth_resamp_exec": (i32, [vp, vp, vp, sz, vp, sz]),
+    "aeth_resamp_prototype": (i32, [sz, sz, sz, vp]),
 }
 
 _lib = None

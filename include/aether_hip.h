@@ -52,6 +52,7 @@ typedef struct aeth_corr aeth_corr;     /* streaming correlator: a matched filte
 typedef struct aeth_seq aeth_seq;       /* LFSR sequences: sequence::generate (src/sequence.rs:47-53) for linear generators */
 typedef struct aeth_chan aeth_chan;     /* polyphase analysis filter bank: windowed, overlapped frames in front of aeth_fft */
 typedef struct aeth_synth aeth_synth;   /* polyphase synthesis filter bank: weighted overlap-add behind aeth_fft */
+typedef struct aeth_resamp aeth_resamp; /* polyphase rational resampler: up U, real FIR, down Q in one pass */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -576,6 +577,65 @@ AETH_API int aeth_synth_exec(aeth_synth *synth, const aeth_cf32 *hist_dev, const
  * AETH_SCALE_N) returns the stream, delayed by ntaps - hop.  A null pointer, a zero size, hop > ntaps or a denominator
  * below 2^-20 (the periodic Hann window at hop == ntaps): AETH_E_ARG, the message names j; nothing is written. */
 AETH_API int aeth_synth_dual_window(const float *w, size_t ntaps, size_t hop, float *out_host);
+
+/* ---- polyphase rational resampler (no body in the reference) ----------------------------------- */
+/* A stream converted by the ratio U / Q with a proper anti-alias / anti-image filter: upsample by U (zero stuffing),
+ * filter with a real FIR h, keep every Q-th sample, in one pass (the reference's rate changes, src/sampling.rs:7-62, are
+ * linear interpolation and sample picking).
+ * An aeth_resamp is made of a REAL prototype h[0 .. T) (host floats, copied), up = U and down = Q.  T = ntaps is a
+ * multiple of U, with P = T / U taps per phase.  U and Q are taken as given: a common factor is not reduced, because the
+ * taps refer to the U that was passed.  U and Q in 1 .. 4096, P in 1 .. 64.
+ *
+ * The stream: s[i] = in_dev[i] for 0 <= i < n; for -(P - 1) <= i < 0 it is hist_dev[P - 1 + i].  When hist_dev is NULL
+ * those samples are +0.0: they are multiplied like any others, as in aeth_synth.  hist_dev is ignored when P == 1.
+ * n must be a multiple of Q.  A call over n = B * Q samples writes exactly B * U outputs: every call therefore starts at
+ * phase 0, and no stream position has to be passed.
+ *
+ * The output is defined bit for bit (f32, no contraction).  For k = 0 .. B * U - 1, with a = floor(k * Q / U) and
+ * r = (k * Q) mod U:
+ *     out[k] = sum over p = 0 .. P - 1, ascending, of  h[p * U + r] * s[a - p]
+ * every product rounded, the sum started from the p = 0 product (not from +0), products added left to right, re and im
+ * independently, each as a real multiplication by the tap.  a <= n - 1 always holds, so every output is complete within
+ * its call: the chunks of a stream concatenate bit for bit when the caller passes the previous P - 1 input samples as
+ * history.
+ *
+ * aeth_resamp_exec is ordered on the context's in-order stream and validates everything before any device work: NULL
+ * pointers AETH_E_ARG; n == 0, n not a multiple of Q, or n_out other than n / Q * U AETH_E_LEN; pointers 8-byte aligned
+ * (AETH_E_ALIGN); the output range clear of the input and the history (AETH_E_ARG); an element count or a grid that
+ * would overflow (n above SIZE_MAX / 16 / U, 2^31 workgroups) AETH_E_UNSUPPORTED.  Element counts are size_t. */
+/* No body in the reference (src/sampling.rs:7-62 has only linear interpolation and sample picking).  ntaps == 0, ntaps
+ * not a multiple of up, up == 0 or down == 0: AETH_E_ARG; P > 64, up > 4096 or down > 4096: AETH_E_UNSUPPORTED; the
+ * message names the offending number, and nothing stays allocated. */
+AETH_API int aeth_resamp_create(aeth_ctx *ctx, const float *taps_host, size_t ntaps, size_t up, size_t down, aeth_resamp **out);
+/* No body in the reference (src/sampling.rs:7-62 resamples without an object).  Waits for the context's stream. */
+AETH_API int aeth_resamp_destroy(aeth_resamp *resamp);
+/* No body in the reference (src/sampling.rs:7-62: the factor is an argument there): U, Q and T; 0 for a null handle. */
+AETH_API size_t aeth_resamp_up(const aeth_resamp *resamp);
+AETH_API size_t aeth_resamp_down(const aeth_resamp *resamp);
+AETH_API size_t aeth_resamp_ntaps(const aeth_resamp *resamp);
+/* No body in the reference (src/sampling.rs:7-62 keeps no state between calls): P - 1, the input samples of history a
+ * call reads. */
+AETH_API size_t aeth_resamp_history(const aeth_resamp *resamp);
+/* No body in the reference (src/sampling.rs:7-62): consecutive outputs one workgroup makes, like aeth_chan_tile: the
+ * launch geometry, for tests that want to cross its edges. */
+AETH_API size_t aeth_resamp_tile(const aeth_resamp *resamp);
+/* No body in the reference (src/sampling.rs:7-62 has one loop): the kernel route, text owned by the object: "staged"
+ * (the inputs of a tile of outputs go through LDS once) or "direct" (strong decimation: every output reads its own P
+ * samples), followed by " u1" when up == 1 (one tap row for every lane).  "" for a null handle. */
+AETH_API const char *aeth_resamp_route(const aeth_resamp *resamp);
+/* No body in the reference (src/sampling.rs:7-62 sizes its output inside the call): n_in / Q * U, or 0 when n_in is not
+ * a multiple of Q, would overflow, or the handle is null. */
+AETH_API size_t aeth_resamp_out_count(const aeth_resamp *resamp, size_t n_in);
+/* No body in the reference (src/sampling.rs:7-62 has only linear interpolation and sample picking): the resampler as
+ * defined above.  8 n bytes read and 8 n U / Q written when every input comes from HBM once. */
+AETH_API int aeth_resamp_exec(aeth_resamp *resamp, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
+                              aeth_cf32 *out_dev, size_t n_out);
+/* No body in the reference (src/sampling.rs:7-62 has no filter).  Host only, needs no context: L = up * taps_per_phase
+ * taps of the low-pass with cutoff 1 / (2 c) cycles per upsampled sample, c = max(up, down), n = 0 .. L - 1:
+ *     sinc((n - (L - 1) / 2) / c) * (0.54 - 0.46 cos(2 pi n / (L - 1)))
+ * scaled so that the taps sum to `up` (unit passband gain after zero stuffing), computed in f64 and rounded once to f32;
+ * the second half mirrors the first bit for bit.  L == 1 gives 1.  A zero size or a null pointer: AETH_E_ARG. */
+AETH_API int aeth_resamp_prototype(size_t up, size_t down, size_t taps_per_phase, float *out_host);
 
 /* ---- pinned host buffers: src/pool.rs:43-221 -------------------------------------------------- */
 /* The reference's object pool ("useful for large buffers and other time expensive objects", :9-10) with pinned

@@ -551,6 +551,44 @@ private:
     aeth_synth *h_ = nullptr;
 };
 
+// ---- polyphase rational resampler (no body in the reference: src/sampling.rs:7-62 interpolates linearly and picks) -----
+// Upsample by `up`, filter with the real taps, keep every `down`-th sample, in one pass: a call over n = B * down samples
+// makes B * up outputs; the previous history() input samples make the chunks of a stream concatenate exactly.
+class Resampler {
+public:
+    Resampler(Context &ctx, const std::vector<float> &taps, size_t up, size_t down)
+    {
+        check(aeth_resamp_create(ctx.get(), taps.data(), taps.size(), up, down, &h_));
+    }
+    ~Resampler() { aeth_resamp_destroy(h_); }
+    Resampler(const Resampler &) = delete;
+    Resampler &operator=(const Resampler &) = delete;
+    // up * taps_per_phase taps of the low-pass at 1 / (2 max(up, down)) cycles per upsampled sample, summing to `up`
+    static std::vector<float> prototype(size_t up, size_t down, size_t taps_per_phase)
+    {
+        const size_t L = up * taps_per_phase;
+        std::vector<float> g(L > 0 ? L : 1);
+        check(aeth_resamp_prototype(up, down, taps_per_phase, g.data()));
+        return g;
+    }
+    size_t up() const { return aeth_resamp_up(h_); }
+    size_t down() const { return aeth_resamp_down(h_); }
+    size_t ntaps() const { return aeth_resamp_ntaps(h_); }
+    size_t history() const { return aeth_resamp_history(h_); }
+    size_t tile() const { return aeth_resamp_tile(h_); }
+    std::string route() const { return aeth_resamp_route(h_); }
+    size_t out_count(size_t n_in) const { return aeth_resamp_out_count(h_, n_in); }
+    // `hist`: the history() samples in front of `x` (null: zeros)
+    void exec(const DeviceVec &x, DeviceVec &out, const DeviceVec *hist = nullptr)
+    {
+        check(aeth_resamp_exec(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), out.ptr(), out.len()));
+    }
+    aeth_resamp *get() const { return h_; }
+
+private:
+    aeth_resamp *h_ = nullptr;
+};
+
 // ---- sequence::expand / sequence::generate for linear generators (src/sequence.rs:18-53) ----------------------------
 // A register is the set of its delays: seq[n] = XOR seq[n - d]; 1 .. 4 registers XORed (Gold codes: two).  `init` holds
 // one word per register, bit i = seq[i] (what expand() unpacks).  Device pointers in and out; bits are one byte each.

@@ -10,6 +10,7 @@ use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_seq { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_chan { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_synth { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_resamp { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
 pub const AETH_POOL_ZERO_ON_RETURN: c_int = 1;
@@ -216,6 +217,19 @@ extern "C" {
     pub fn aeth_synth_exec(synth: *mut aeth_synth, hist_dev: *const cf32, spec_dev: *const cf32, n_in: usize, first_frame: u64,
                            sign: c_int, scale_kind: c_int, x: c_float, out_dev: *mut cf32, n_out: usize) -> c_int;
     pub fn aeth_synth_dual_window(w: *const c_float, ntaps: usize, hop: usize, out_host: *mut c_float) -> c_int;
+    pub fn aeth_resamp_create(ctx: *mut aeth_ctx, taps_host: *const c_float, ntaps: usize, up: usize, down: usize,
+                              out: *mut *mut aeth_resamp) -> c_int;
+    pub fn aeth_resamp_destroy(resamp: *mut aeth_resamp) -> c_int;
+    pub fn aeth_resamp_up(resamp: *const aeth_resamp) -> usize;
+    pub fn aeth_resamp_down(resamp: *const aeth_resamp) -> usize;
+    pub fn aeth_resamp_ntaps(resamp: *const aeth_resamp) -> usize;
+    pub fn aeth_resamp_history(resamp: *const aeth_resamp) -> usize;
+    pub fn aeth_resamp_tile(resamp: *const aeth_resamp) -> usize;
+    pub fn aeth_resamp_route(resamp: *const aeth_resamp) -> *const c_char;
+    pub fn aeth_resamp_out_count(resamp: *const aeth_resamp, n_in: usize) -> usize;
+    pub fn aeth_resamp_exec(resamp: *mut aeth_resamp, hist_dev: *const cf32, in_dev: *const cf32, n: usize, out_dev: *mut cf32,
+                            n_out: usize) -> c_int;
+    pub fn aeth_resamp_prototype(up: usize, down: usize, taps_per_phase: usize, out_host: *mut c_float) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;

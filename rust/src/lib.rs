@@ -338,6 +338,37 @@ impl<'c> Synthesizer<'c> {
 }
 impl<'c> Drop for Synthesizer<'c> { fn drop(&mut self) { unsafe { aeth_synth_destroy(self.h); } } }
 
+/// Polyphase rational resampler (no body in the reference: src/sampling.rs:7-62 has only linear interpolation and sample
+/// picking): upsample by `up`, filter with the real taps, keep every `down`-th sample, in one pass.  A call over
+/// n = B * down samples makes B * up outputs; the previous `history()` input samples make chunks concatenate exactly.
+pub struct Resampler<'c> { h: *mut aeth_resamp, _ctx: PhantomData<&'c Context> }
+impl<'c> Resampler<'c> {
+    pub fn new(ctx: &'c Context, taps: &[f32], up: usize, down: usize) -> Resampler<'c> {
+        let mut h = ptr::null_mut();
+        check(unsafe { aeth_resamp_create(ctx.h, taps.as_ptr(), taps.len(), up, down, &mut h) });
+        Resampler { h, _ctx: PhantomData }
+    }
+    /// `up * taps_per_phase` taps of the low-pass at 1 / (2 max(up, down)) cycles per upsampled sample, summing to `up`
+    pub fn prototype(up: usize, down: usize, taps_per_phase: usize) -> Vec<f32> {
+        let mut g = vec![0f32; up * taps_per_phase];
+        check(unsafe { aeth_resamp_prototype(up, down, taps_per_phase, g.as_mut_ptr()) });
+        g
+    }
+    pub fn up(&self) -> usize { unsafe { aeth_resamp_up(self.h) } }
+    pub fn down(&self) -> usize { unsafe { aeth_resamp_down(self.h) } }
+    pub fn ntaps(&self) -> usize { unsafe { aeth_resamp_ntaps(self.h) } }
+    /// input samples in front of a call's first that reach into its output: taps per phase - 1
+    pub fn history(&self) -> usize { unsafe { aeth_resamp_history(self.h) } }
+    pub fn tile(&self) -> usize { unsafe { aeth_resamp_tile(self.h) } }
+    pub fn route(&self) -> String { unsafe { std::ffi::CStr::from_ptr(aeth_resamp_route(self.h)) }.to_string_lossy().into_owned() }
+    pub fn out_count(&self, n_in: usize) -> usize { unsafe { aeth_resamp_out_count(self.h, n_in) } }
+    /// `hist`: the history() samples in front of `x` (None: zeros)
+    pub fn exec(&mut self, x: &DeviceVec, hist: Option<&DeviceVec>, out: &mut DeviceVec) {
+        check(unsafe { aeth_resamp_exec(self.h, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n, out.p, out.n) });
+    }
+}
+impl<'c> Drop for Resampler<'c> { fn drop(&mut self) { unsafe { aeth_resamp_destroy(self.h); } } }
+
 /// The device counterpart of `pipeline::new().add_stage(..)` (src/pipeline.rs:24-41, :123-137): five fixed stages --
 /// copy-in | upload | compute | download | copy-out -- whose compute stage is one of the library's device ops (a closure
 /// cannot cross the C ABI).  `run` takes host slices and returns what `aeth_stream_host` reports.
