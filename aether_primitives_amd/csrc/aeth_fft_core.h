@@ -585,31 +585,16 @@ __global__ void build_lane_twiddles(const cf *__restrict__ twN, cf *__restrict__
 // read k; image k is next written only after the barrier of exchange k+1, which every
 // lane passes after it has finished reading image k).  With a single image a second
 // barrier in front of the writes keeps late readers safe.
-// XP (tuning): bit 0: the exchange runs at s_setprio 1, the butterflies at 0; bit 1: no barriers, bit 2: no LDS
-// traffic at all (both diagnosis only, wrong results)
-// XP bit 4 (16): raw `s_barrier` behind an explicit lgkmcnt(0) instead of __syncthreads(): the fence of __syncthreads()
-// drains vmcnt(0) whenever an LDS-DMA (a pending LDS write on the VM counter) is in flight, which would make every
-// exchange wait for the window that is still landing (aeth_fir_kernel.h, V_DMA)
-template <int XP> __device__ __forceinline__ void wg_barrier()
-{
-    if constexpr (XP & 16) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    } else __syncthreads();
-}
-
+// XP (tuning): bit 0 (1): the exchange runs at s_setprio 1, the butterflies at 0; bit 3 (8): XOR-swizzled image (pidx)
 template <class C, int PASS, int S, int PAR, int XP = 0>
 __device__ __forceinline__ void run_pass(cf (&w)[C::P], const cf (&tw)[C::TW], cf *__restrict__ lds, int tid)
 {
     constexpr int R = C::radix(PASS), B = C::P / R, p = C::pbefore(PASS);
     constexpr bool last = (PASS == C::NPASS - 1);
-    constexpr bool NOLDS = (XP & 4) != 0;
     cf *img = lds;
-    if constexpr (!last && !NOLDS) {
+    if constexpr (!last) {
         if constexpr (C::DB) img = lds + (((PAR + PASS) & 1) ? C::LDS_ELEMS : 0);
-        else if constexpr (XP & 2) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        else wg_barrier<XP>();              // earlier readers of the single image are done
+        else __syncthreads();               // earlier readers of the single image are done
     }
 #pragma unroll
     for (int b = 0; b < B; b++) {
@@ -621,7 +606,7 @@ __device__ __forceinline__ void run_pass(cf (&w)[C::P], const cf (&tw)[C::TW], c
             for (int r = 1; r < R; r++) u[r] = ctw<S>(u[r], tw[C::twoff(PASS) + b * (R - 1) + (r - 1)]);
         }
         Bfly<R, S>::run(u);
-        if constexpr (last || NOLDS) {
+        if constexpr (last) {
 #pragma unroll
             for (int r = 0; r < R; r++) w[b + r * B] = u[r];
         } else {
@@ -632,10 +617,9 @@ __device__ __forceinline__ void run_pass(cf (&w)[C::P], const cf (&tw)[C::TW], c
             for (int r = 0; r < R; r++) img[pidx<XP>(j + r * p)] = u[r];
         }
     }
-    if constexpr (!last && !NOLDS) {
+    if constexpr (!last) {
         if constexpr (XP & 1) __builtin_amdgcn_s_setprio(1);
-        if constexpr (XP & 2) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        else wg_barrier<XP>();
+        __syncthreads();
 #pragma unroll
         for (int m = 0; m < C::P; m++) w[m] = img[pidx<XP>(tid + m * C::T)];
         if constexpr (XP & 1) __builtin_amdgcn_s_setprio(0);

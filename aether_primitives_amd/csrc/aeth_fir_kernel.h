@@ -2,7 +2,10 @@
 // and the reference citations; tools/fir_lab.hip instantiates the same template for A/B measurements).
 //
 // One 128-lane workgroup per overlap-save block (N = 2048: 16 points per lane), persistent loop over blocks,
-// the next block's window prefetched into registers while the current one is transformed.
+// the next block's window prefetched into registers while the current one is transformed.  Every build of
+// fmi_kernel that this header allows is one libaether_hip.so launches or tools/fir_lab.hip measures; the block's
+// results leave as samples (store_block), bit bytes (demod_block), levels (level_block) or one peak record per wave
+// (peak_block).
 #pragma once
 
 #include "aeth_internal.h"
@@ -56,55 +59,29 @@ struct FmiArgs {
     PeakPart *parts = nullptr;
 };
 
-// Kernel variants (template parameter VAR, a bit set).  0 is the round-1 kernel.
+// Kernel variants (template parameter VAR, a bit set).  0 is the round-1 kernel.  The first three shape the transform
+// and the prefetch, the others replace the sample store; launch_fmi (aeth_fir.hip) decides which launch takes which.
+// The values are part of the mangled kernel names, which tests/test_corr_resources.py, tools/variant_coverage.py and
+// tools/summarize_profile.py parse, so they stay as they are: the gaps are variants that were measured and removed
+// (profiles/).
 enum : int {
-    V_PEEL  = 1,    // first block peeled out of the loop: window 0 is waited for alone (counted vmcnt), the tables
-                    // and window 1 land under the first transform instead of in front of it
-    V_TOUCH = 2,    // one 4-byte load per 128-byte line of the window two rounds ahead: pulls it into L2 / the
-                    // Infinity Cache so that the register prefetch one round later is served on-die
-    V_PRIO  = 4,    // s_setprio 1 around every LDS exchange (its latency chain is what a block's time is made of)
-    V_TOUCH3 = 8,   // with V_TOUCH: three rounds ahead instead of two
-    V_DECIM = 512,  // product variant: decimating store (aeth_fir_exec_decim)
-    V_UNROLL2 = 4096, // the block loop unrolled by two with the roles of the two window register sets swapped (no copy)
-    V_XOR = 2048,   // XOR-swizzled LDS exchange image instead of the padded one (see aeth_fft_core.h: pidx)
-    V_XCD = 8192,   // lab only, measured negative (54.1 -> 55.5 us, two queues 48.5 -> 50.2): workgroups of one XCD
-                    // (blockIdx % 8) take ADJACENT blocks of a round, so that the 63-sample halo a block shares with
-                    // its neighbour is read through the same L2 -- round-robin over the XCDs spreads every region of
-                    // the stream over all eight L2s and wins
-    V_SPREAD = 16384, // the next window's 16 loads issued in four groups between the passes of this block's forward
-                    // transform instead of one burst in front of it (the TA command FIFO is full 40 % of the time)
-    V_DEMOD = 1024, // product variant: hard demodulation instead of the sample store (aeth_fft_mul_ifft_demod)
-    V_DM_BPSK = 1 << 16, V_DM_QGEN = 1 << 17,   // with V_DEMOD: the decision's mode (neither: QPSK, separable table)
-    V_LEVEL = 1 << 19, // product variant: a 4-byte level of every output sample instead of the sample (aeth_corr_exec_levels)
+    V_PRIO   = 4,       // s_setprio 1 around every LDS exchange (its latency chain is what a block's time is made of)
+    V_XOR    = 2048,    // XOR-swizzled LDS exchange image instead of the padded one (see aeth_fft_core.h: pidx)
+    V_SPREAD = 16384,   // the next window's 16 loads issued in four groups between the passes of this block's forward
+                        // transform instead of one burst in front of it (the TA command FIFO is full 40 % of the time)
+    V_DECIM  = 512,     // decimating store (aeth_fir_exec_decim)
+    V_DEMOD  = 1024,    // hard demodulation instead of the sample store (aeth_fft_mul_ifft_demod)
+    V_DM_BPSK = 1 << 16, V_DM_QGEN = 1 << 17,     // with V_DEMOD: the decision's mode (neither: QPSK, separable table)
+    V_LEVEL  = 1 << 19, // a 4-byte level of every output sample instead of the sample (aeth_corr_exec_levels)
     V_LV_DB = 1 << 20, V_LV_POWER_DB = 1 << 21,   // with V_LEVEL: the level kind (neither: AETH_LEVEL_NORM)
-    V_PEAK = 1 << 22, // product variant: the block's largest |c|^2 instead of any store (aeth_corr_search)
-    V_DMA = 1 << 18, // the next window goes straight into a 16 KiB LDS landing image (buffer_load_dwordx4 ... lds: 8 pieces
-                    // of 1 KiB per wave and block instead of 16 register loads) and is read from there at the start of its
-                    // own iteration: no prefetch registers, no register copy per block; paid for with ONE exchange image
-                    // (two barriers per exchange) so that four workgroups still fit a CU.  N = 2048 (two waves) only.
-    V_NOLOAD = 16,  // diagnosis only (wrong output): no window loads inside the loop
-    V_NOSTORE = 32, // diagnosis only (wrong output): no output stores inside the loop
-    V_CENSUS = 256, // diagnosis only: every wave records HW_ID / XCC_ID in the buffer passed as `chirp`
-    V_NOLDS = 128,  // diagnosis only (wrong output): no LDS exchanges at all
-    V_NOBAR = 64,   // diagnosis only (wrong output): LDS exchanges without workgroup barriers
+    V_PEAK   = 1 << 22, // the block's largest |c|^2 instead of any store (aeth_corr_search)
 };
+constexpr int V_ALL = V_PRIO | V_XOR | V_SPREAD | V_DECIM | V_DEMOD | V_DM_BPSK | V_DM_QGEN | V_LEVEL | V_LV_DB | V_LV_POWER_DB |
+                      V_PEAK;
 
-// What libaether_hip.so may instantiate; everything else is measurement / diagnosis and builds only where
-// AETH_FIR_LAB is defined non-zero before this header is included (tools/fir_lab.hip)
-constexpr int V_PRODUCT_MASK = V_PRIO | V_XOR | V_SPREAD | V_DECIM | V_DEMOD | V_DM_BPSK | V_DM_QGEN | V_LEVEL | V_LV_DB |
-                               V_LV_POWER_DB | V_PEAK;
-#ifndef AETH_FIR_LAB
-#define AETH_FIR_LAB 0
-#endif
-
-// cache-policy bits of the streamed accesses (aux operand of the buffer instructions: 1 = sc0, 2 = nt, 16 = sc1);
-// macros so that tools/fir_lab can be built with other choices
-#ifndef AETH_FIR_LOAD_AUX
-#define AETH_FIR_LOAD_AUX 2
-#endif
-#ifndef AETH_FIR_STORE_AUX
-#define AETH_FIR_STORE_AUX 18
-#endif
+// cache-policy bits of the streamed accesses (aux operand of the buffer instructions: 1 = sc0, 2 = nt, 16 = sc1):
+// loads nt, stores nt + sc1 (tools/nt_modes.hip: 6.55 against 6.43 TB/s for nt alone)
+constexpr int kLoadAux = 2, kStoreAux = 18;
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -134,7 +111,7 @@ __device__ __forceinline__ void load_window(cf (&x)[C::P], const FmiArgs &a, lon
             auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
             for (int m = 0; m < C::P; m++)
-                x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? AETH_FIR_LOAD_AUX : 0));
+                x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? kLoadAux : 0));
             // (the window's oldest ov-nhist samples are zeroed when the window is consumed: doing it
             // here would put a wait for the load right behind its issue)
             return;
@@ -189,7 +166,7 @@ __device__ __forceinline__ void load_window_srd(cf (&x)[C::P], const FmiArgs &a,
     auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
     for (int m = 0; m < C::P; m++)
-        x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? AETH_FIR_LOAD_AUX : 0));
+        x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? kLoadAux : 0));
 }
 
 // the same, slots [M0, M1) only (V_SPREAD: the window arrives in four instalments)
@@ -203,57 +180,8 @@ __device__ __forceinline__ void load_window_srd_part(cf (&x)[C::P], const FmiArg
     auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
     for (int m = M0; m < M1; m++)
-        x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? AETH_FIR_LOAD_AUX : 0));
+        x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? kLoadAux : 0));
     __builtin_amdgcn_sched_barrier(0);
-}
-
-// ---- V_DMA: the window through an LDS landing image ---------------------------------------------------------
-// The image is lane-linear per wave-instruction (LDS dest = base + lane * 16), so the permutation sits on the SOURCE
-// side: piece j of wave wv fetches the 512-byte runs of window rows m = 2j and 2j+1 (a row = T elements = 1 KiB) that
-// this very wave reads in pass 0 (element tid + m*T).  No wave reads what another wave landed, so the issuing wave's
-// own vmcnt orders its ds_reads behind the DMA and no barrier is needed.  A lane past the descriptor's range lands
-// zeros (tools/shape_ab.hip, oob_probe), so the ragged end of the stream and a non-existent block need no branch.
-typedef __attribute__((address_space(3))) void *lds_vptr_t;
-template <bool NT>
-__device__ __forceinline__ void dma_piece(__amdgpu_buffer_rsrc_t rs, cf *dst, int voff, int soff)
-{
-#if __HIP_DEVICE_COMPILE__
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr_t)dst, 16, voff, soff, 0, NT ? AETH_FIR_LOAD_AUX : 0);
-#endif
-}
-template <class C, bool NT, int J0, int J1>
-__device__ __forceinline__ void dma_window_part(cf *land, const FmiArgs &a, long long blk, int tid)
-{
-    static_assert(C::T == 128 && C::P == 16, "landing image: two waves, sixteen rows of 1 KiB");
-    const bool active = blk < a.nblocks;
-    const long long win0 = active ? blk * a.hop - a.ov : 0;
-    long long left = a.n - win0;
-    const int bytes = active ? (int)(left < a.frame_n ? left : a.frame_n) * 8 : 0;
-    auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
-    const int wv = tid >> 6, l = tid & 63;
-    const int voff = (l >> 5) * 1024 + wv * 512 + (l & 31) * 16;
-#pragma unroll
-    for (int j = J0; j < J1; j++) dma_piece<NT>(rs, land + wv * 1024 + j * 128, voff, j * 2048);
-    __builtin_amdgcn_sched_barrier(0);
-}
-// slot of window element tid + m*T in the landing image (elements)
-template <class C> __device__ __forceinline__ int land_slot(int tid, int m) { return (tid >> 6) * 1024 + (m >> 1) * 128 + (m & 1) * 64 + (tid & 63); }
-
-// V_TOUCH: one dword per 128-byte line of block `blk`'s window (plain cache policy: the line is meant to stay on
-// the die until the register prefetch reads it); the value is never used, the caller only keeps it alive.
-template <class C>
-__device__ __forceinline__ unsigned touch_window(const FmiArgs &a, long long blk, int tid)
-{
-    const bool active = blk < a.nblocks;
-    const long long win0 = active ? blk * a.hop - a.ov : 0;
-    long long left = a.n - win0;
-    const int bytes = active ? (int)(left < a.frame_n ? left : a.frame_n) * 8 : 0;
-    auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
-    unsigned acc = 0;
-#pragma unroll
-    for (int off = 0; off < C::N * 8; off += C::T * 128)
-        acc |= __builtin_amdgcn_raw_buffer_load_b32(rs, off + tid * 128, 0, 0);
-    return acc;
 }
 
 // Modulation::demod_naive on the block's output samples (modulation.rs:33-56 for [cf32; 4], :133-144 for [cf32; 2]):
@@ -340,8 +268,8 @@ __device__ __forceinline__ void demod_block(const cf (&w)[C::P], const FmiArgs &
         const int off = (e >= a.ov) ? e * B : 0x7ffffff0;
         const cf v = SCALED ? cscale_k(w[m], ss) : w[m];
         const unsigned o = demod_decide<DM>(v, k);
-        if constexpr (B == 1) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)o, rs, off, 0, NT ? AETH_FIR_STORE_AUX : 0);
-        else __builtin_amdgcn_raw_buffer_store_b16((unsigned short)o, rs, off, 0, NT ? AETH_FIR_STORE_AUX : 0);
+        if constexpr (B == 1) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)o, rs, off, 0, NT ? kStoreAux : 0);
+        else __builtin_amdgcn_raw_buffer_store_b16((unsigned short)o, rs, off, 0, NT ? kStoreAux : 0);
     }
 }
 
@@ -365,7 +293,7 @@ __device__ __forceinline__ void level_block(const cf (&w)[C::P], const FmiArgs &
         const int off = (e >= a.ov) ? e * 4 : 0x7ffffff0;
         const cf v = SCALED ? cscale_k(w[m], ss) : w[m];
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, aeth::level_of<KIND>(v.x, v.y)), rs, off, 0,
-                                              NT ? AETH_FIR_STORE_AUX : 0);
+                                              NT ? kStoreAux : 0);
     }
 }
 
@@ -410,7 +338,7 @@ __device__ __forceinline__ void peak_block(const cf (&w)[C::P], const FmiArgs &a
     const unsigned long long qb = __builtin_bit_cast(unsigned long long, bq);
     u32x4 r; r.x = (unsigned)qb; r.y = (unsigned)(qb >> 32); r.z = be; r.w = nn;
     const int off = (tid & 63) == 0 ? (tid >> 6) * 16 : 0x7ffffff0;
-    __builtin_amdgcn_raw_buffer_store_b128(r, rs, off, 0, NT ? AETH_FIR_STORE_AUX : 0);
+    __builtin_amdgcn_raw_buffer_store_b128(r, rs, off, 0, NT ? kStoreAux : 0);
 }
 
 // CHECK = false: the caller knows that the block exists (no branch around the stores, so that hipcc keeps
@@ -438,7 +366,7 @@ __device__ __forceinline__ void store_block(const cf (&w)[C::P], const FmiArgs &
             const bool keep = e >= a.ov && q * a.dec.d == o && (long long)o < a.n;
             const int off = keep ? (int)(q - q0) * 8 : 0x7ffffff0;
             cf v = SCALED ? cscale_k(w[m], ss) : w[m];
-            __builtin_amdgcn_raw_buffer_store_b64(as_u32x2(v), rs, off, 0, NT ? AETH_FIR_STORE_AUX : 0);
+            __builtin_amdgcn_raw_buffer_store_b64(as_u32x2(v), rs, off, 0, NT ? kStoreAux : 0);
         }
     } else if constexpr (C::F == 1) {
         long long left = a.n - base;
@@ -453,7 +381,7 @@ __device__ __forceinline__ void store_block(const cf (&w)[C::P], const FmiArgs &
             const int e = tid + m * C::T;
             const int off = (e >= a.ov) ? e * 8 : 0x7ffffff0;
             cf v = SCALED ? cscale_k(w[m], ss) : w[m];
-            __builtin_amdgcn_raw_buffer_store_b64(as_u32x2(v), rs, off, 0, NT ? AETH_FIR_STORE_AUX : 0);   // nt + sc1: streamed stores (tools/nt_modes.hip: 6.55 vs 6.43 TB/s for nt alone)
+            __builtin_amdgcn_raw_buffer_store_b64(as_u32x2(v), rs, off, 0, NT ? kStoreAux : 0);   // nt + sc1: streamed stores (tools/nt_modes.hip: 6.55 vs 6.43 TB/s for nt alone)
         }
     } else {
 #pragma unroll
@@ -490,7 +418,7 @@ template <class C, bool SCALED, bool BLU, int VAR>
 __device__ __forceinline__ void transform_block(cf (&w)[C::P], const cf (&tw)[C::TW], const cf (&H)[C::P],
                                                 cf *__restrict__ lds, const FmiArgs &a, int tid)
 {
-    constexpr int XP = ((VAR & V_PRIO) ? 1 : 0) | ((VAR & V_NOBAR) ? 2 : 0) | ((VAR & V_NOLDS) ? 4 : 0) | ((VAR & V_XOR) ? 8 : 0);
+    constexpr int XP = ((VAR & V_PRIO) ? 1 : 0) | ((VAR & V_XOR) ? 8 : 0);
     if constexpr (BLU) {
         // x[n] (conjugated for the other exponent sign) * chirp[n]; chirp is 0 beyond the frame (descriptor range)
         auto cr = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.chirp), 0, a.frame_n * 8, 0x00020000);
@@ -528,25 +456,13 @@ __device__ __forceinline__ void transform_block(cf (&w)[C::P], const cf (&tw)[C:
 template <class C, bool SCALED, int MINW, bool NT, bool BLU, int VAR = 0>
 __global__ __launch_bounds__(C::WG, MINW) void fmi_kernel(FmiArgs a)
 {
-    static_assert(AETH_FIR_LAB || (VAR & ~V_PRODUCT_MASK) == 0, "lab-only kernel variant in a product build");
+    static_assert((VAR & ~V_ALL) == 0, "VAR names a kernel variant that does not exist");
     __shared__ cf lds_all[C::LDS_TOTAL];
     // F == 1: the whole workgroup is one frame, so the block index stays provably wave-uniform
     const int tid = (C::F == 1) ? (int)threadIdx.x : (int)(threadIdx.x % C::T);
     const int fl = (C::F == 1) ? 0 : (int)(threadIdx.x / C::T);
     cf *lds = lds_all + fl * C::LDS_FRAME;
-
-    if constexpr (VAR & V_CENSUS) {
-        if ((threadIdx.x & 63) == 0) {
-            unsigned *cb = reinterpret_cast<unsigned *>(const_cast<cf *>(a.chirp));
-            const unsigned slot = blockIdx.x * (C::WG / 64) + threadIdx.x / 64;
-            cb[2 * slot] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));      // HW_REG_HW_ID, all 32 bits
-            cb[2 * slot + 1] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));  // HW_REG_XCC_ID
-        }
-    }
     const long long ngroups = (a.nblocks + C::F - 1) / C::F;
-    constexpr bool PEEL = (VAR & V_PEEL) && C::F == 1 && !BLU;
-    constexpr bool TOUCH = (VAR & V_TOUCH) && C::F == 1 && !BLU;
-    constexpr int TOUCH_AHEAD = (VAR & V_TOUCH3) ? 3 : 2;
     cf nx[C::P], tw[C::TW], H[C::P];
     constexpr int DM = (VAR & V_DM_BPSK) ? DM_BPSK : (VAR & V_DM_QGEN) ? DM_QGEN : DM_QSEP;
     static_assert(!(VAR & (V_DM_BPSK | V_DM_QGEN)) || (VAR & V_DEMOD), "decision mode without V_DEMOD");
@@ -554,69 +470,22 @@ __global__ __launch_bounds__(C::WG, MINW) void fmi_kernel(FmiArgs a)
     if constexpr (VAR & V_DEMOD) dk = demod_consts<DM>(a);
     constexpr int LK = (VAR & V_LV_DB) ? AETH_LEVEL_DB : (VAR & V_LV_POWER_DB) ? AETH_LEVEL_POWER_DB : AETH_LEVEL_NORM;
     static_assert(!(VAR & (V_LV_DB | V_LV_POWER_DB)) || (VAR & V_LEVEL), "level kind without V_LEVEL");
-    static_assert(!(VAR & (V_LEVEL | V_PEAK)) || (C::F == 1 && !BLU && !(VAR & (V_PEEL | V_UNROLL2 | V_DEMOD | V_DECIM))),
+    static_assert(!(VAR & (V_LEVEL | V_PEAK)) || (C::F == 1 && !BLU && !(VAR & (V_DEMOD | V_DECIM))),
                   "level store / peak search: the plain loop of one-block workgroups");
-    unsigned bid = blockIdx.x;
-    if constexpr ((VAR & V_XCD) != 0) {
-        if ((gridDim.x & 7u) == 0) bid = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    }
-    long long g0 = bid;
-    unsigned tprev = 0;     // V_TOUCH: the previous round's touch result, kept alive until the next round (never used)
-
-    if constexpr (PEEL) {
-        // Block 0 of this workgroup outside the loop.  Issue order = return order: window 0, tables, window 1.  The
-        // first pass needs window 0 only, so its wait leaves the tables and the next window in flight; they land
-        // while pass 0 and the first exchange run.
-        cf w[C::P];
-        if (bid == 0) load_window<C, NT>(w, a, 0, tid);     // history / zero initial state: predicated path
-        else load_window_srd<C, NT>(w, a, g0, tid);
-        if (a.twL) load_twiddles_lane<C>(tw, a.twL, tid);
-        else load_twiddles<C>(tw, a.twN, tid);
+    // software pipeline: the next block's window is in flight while this one is transformed.
+    // The first window goes out before the (L2-resident) tables so the HBM fetch starts at once.
+    load_window<C, NT>(nx, a, (long long)blockIdx.x * C::F + fl, tid);
+    if (a.twL) load_twiddles_lane<C>(tw, a.twL, tid);
+    else load_twiddles<C>(tw, a.twN, tid);
 #pragma unroll
-        for (int m = 0; m < C::P; m++) H[m] = a.Hf[tid + m * C::T];
-        load_window_srd<C, NT>(nx, a, g0 + gridDim.x, tid);
-        if constexpr (TOUCH) {
-#pragma unroll
-            for (int k = 2; k <= TOUCH_AHEAD; k++) tprev |= touch_window<C>(a, g0 + (long long)k * gridDim.x, tid);
-        }
-        if (tid < a.ov - a.nhist) w[0] = mk(0.f, 0.f);
-        transform_block<C, SCALED, BLU, VAR>(w, tw, H, lds, a, tid);
-        if constexpr (VAR & V_DEMOD) demod_block<C, SCALED, NT, DM>(w, a, dk, g0, tid);
-        else store_block<C, SCALED, NT, false, (VAR & V_DECIM) != 0>(w, a, g0, tid);     // grid <= ngroups: the block exists
-        g0 += gridDim.x;
-    } else {
-        // software pipeline: the next block's window is in flight while this one is transformed.
-        // The first window goes out before the (L2-resident) tables so the HBM fetch starts at once.
-        load_window<C, NT>(nx, a, (long long)bid * C::F + fl, tid);
-        if (a.twL) load_twiddles_lane<C>(tw, a.twL, tid);
-        else load_twiddles<C>(tw, a.twN, tid);
-#pragma unroll
-        for (int m = 0; m < C::P; m++) H[m] = a.Hf[tid + m * C::T];
-        // Drain the table loads HERE, once.  Otherwise hipcc places their counted waits at the first
-        // uses inside the loop body, where they run every iteration and end in vmcnt(0) halfway
-        // through each block -- forcing the prefetched window AND the previous block's stores to
-        // complete there instead of riding under the whole block.
-        __builtin_amdgcn_s_waitcnt(0x0F70);                     // vmcnt(0) only
-    }
-    if constexpr ((VAR & V_UNROLL2) && C::F == 1 && !BLU && !(VAR & (V_DEMOD | V_DECIM | V_TOUCH | V_NOLOAD | V_NOSTORE))) {
-        // two blocks per trip: window registers A (= nx) and B swap roles, so no block starts with a 32-register copy.
-        // Everything stays branch-free (blocks past the end load and store through zero-length descriptors).
-        cf wb[C::P];
-        auto one = [&](cf (&cur)[C::P], cf (&nxt)[C::P], long long g) {
-            if (tid < a.ov - a.nhist) cur[0] = mk(0.f, 0.f);
-            load_window_srd<C, NT>(nxt, a, g + gridDim.x, tid);
-            transform_block<C, SCALED, BLU, VAR>(cur, tw, H, lds, a, tid);
-            store_block<C, SCALED, NT, false, false>(cur, a, g, tid);
-        };
+    for (int m = 0; m < C::P; m++) H[m] = a.Hf[tid + m * C::T];
+    // Drain the table loads HERE, once.  Otherwise hipcc places their counted waits at the first
+    // uses inside the loop body, where they run every iteration and end in vmcnt(0) halfway
+    // through each block -- forcing the prefetched window AND the previous block's stores to
+    // complete there instead of riding under the whole block.
+    __builtin_amdgcn_s_waitcnt(0x0F70);                     // vmcnt(0) only
 #pragma unroll 1
-        for (long long g = g0; g < ngroups; g += 2 * (long long)gridDim.x) {
-            one(nx, wb, g);
-            one(wb, nx, g + gridDim.x);
-        }
-        return;
-    }
-#pragma unroll 1
-    for (long long g = g0; g < ngroups; g += gridDim.x) {
+    for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
         const long long blk = g * C::F + fl;
         cf w[C::P];
 #pragma unroll
@@ -626,10 +495,7 @@ __global__ __launch_bounds__(C::WG, MINW) void fmi_kernel(FmiArgs a)
         // (history = ntaps-1 samples) then reproduce the unsharded run bit for bit
         if constexpr (C::F == 1) { if (tid < a.ov - a.nhist) w[0] = mk(0.f, 0.f); }
         const long long gn = g + gridDim.x;
-        if constexpr (VAR & V_NOLOAD) {
-#pragma unroll
-            for (int m = 0; m < C::P; m++) asm volatile("" : "+v"(nx[m]));     // opaque, so that nothing folds
-        } else if constexpr (C::F == 1 && (VAR & V_SPREAD) && !SCALED && !BLU) {
+        if constexpr (C::F == 1 && (VAR & V_SPREAD) && !SCALED && !BLU) {
             // (loads issued inside transform_block_spread)
         } else if constexpr (C::F == 1) {
             // gn >= gridDim.x >= 1, so the window never starts before the stream: descriptor path
@@ -637,79 +503,12 @@ __global__ __launch_bounds__(C::WG, MINW) void fmi_kernel(FmiArgs a)
         } else {
             if (gn < ngroups) load_window<C, NT>(nx, a, gn * C::F + fl, tid);
         }
-        if constexpr (TOUCH) {
-            asm volatile("" ::"v"(tprev));      // issued a whole round ago: no wait
-            tprev = touch_window<C>(a, g + (long long)TOUCH_AHEAD * gridDim.x, tid);
-        }
         if constexpr (C::F == 1 && (VAR & V_SPREAD) && !SCALED && !BLU) transform_block_spread<C, NT, VAR>(w, nx, tw, H, lds, a, gn, tid);
         else transform_block<C, SCALED, BLU, VAR>(w, tw, H, lds, a, tid);
-        if constexpr (VAR & V_NOSTORE) {
-#pragma unroll
-            for (int m = 0; m < C::P; m++) asm volatile("" ::"v"(w[m]));
-        } else if constexpr (VAR & V_DEMOD) demod_block<C, SCALED, NT, DM>(w, a, dk, blk, tid);
+        if constexpr (VAR & V_DEMOD) demod_block<C, SCALED, NT, DM>(w, a, dk, blk, tid);
         else if constexpr (VAR & V_LEVEL) level_block<C, SCALED, NT, LK>(w, a, blk, tid);
         else if constexpr (VAR & V_PEAK) peak_block<C, SCALED, NT>(w, a, blk, tid);
         else store_block<C, SCALED, NT, true, (VAR & V_DECIM) != 0>(w, a, blk, tid);
-    }
-    if constexpr (TOUCH) asm volatile("" ::"v"(tprev));
-}
-
-// ---- V_DMA build of the FIR kernel (N = 2048: two waves, sixteen 1 KiB window rows; unscaled, no chirp) ----------
-template <class C> struct OneImg : C { static constexpr bool DB = false; static constexpr int LDS_TOTAL = C::LDS_ELEMS; };
-
-template <class C0, bool NT, int VAR>
-__global__ __launch_bounds__(C0::WG, 1) void fmi_dma_kernel(FmiArgs a)
-{
-    using C = OneImg<C0>;
-    static_assert(C::F == 1 && C::T == 128 && C::P == 16 && C::NPASS == 3, "landing image layout: N = 2048");
-    static_assert(AETH_FIR_LAB || (VAR & ~V_PRODUCT_MASK) == 0, "lab-only kernel variant in a product build");
-    __shared__ __attribute__((aligned(1024))) cf lds_all[C::N + C::LDS_TOTAL];
-    cf *land = lds_all, *lds = lds_all + C::N;              // [landing image | one exchange image]
-    const int tid = (int)threadIdx.x;
-    constexpr int XP = ((VAR & V_PRIO) ? 1 : 0) | ((VAR & V_XOR) ? 8 : 0) | 16;     // raw barriers: a DMA is always in flight
-    cf tw[C::TW], H[C::P];
-    const long long g0 = blockIdx.x;
-    if (blockIdx.x == 0) {
-        // history / zero initial state: predicated register path, parked in the landing image in the DMA's layout
-        cf w0[C::P];
-        load_window<C, NT>(w0, a, 0, tid);
-#pragma unroll
-        for (int m = 0; m < C::P; m++) land[land_slot<C>(tid, m)] = w0[m];
-    } else dma_window_part<C, NT, 0, 8>(land, a, g0, tid);
-    if (a.twL) load_twiddles_lane<C>(tw, a.twL, tid);
-    else load_twiddles<C>(tw, a.twN, tid);
-#pragma unroll
-    for (int m = 0; m < C::P; m++) H[m] = a.Hf[tid + m * C::T];
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // tables and the first window are in
-#pragma unroll 1
-    for (long long g = g0; g < a.nblocks; g += gridDim.x) {
-        cf w[C::P];
-#pragma unroll
-        for (int m = 0; m < C::P; m++) w[m] = land[land_slot<C>(tid, m)];
-        if (tid < a.ov - a.nhist) w[0] = mk(0.f, 0.f);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the image is read out before the next window lands in it
-        __builtin_amdgcn_sched_barrier(0);
-        const long long gn = g + gridDim.x;
-        if constexpr (VAR & V_SPREAD) {
-            dma_window_part<C, NT, 0, 2>(land, a, gn, tid);
-            run_pass<C, 0, +1, 0, XP>(w, tw, lds, tid);
-            dma_window_part<C, NT, 2, 4>(land, a, gn, tid);
-            run_pass<C, 1, +1, 0, XP>(w, tw, lds, tid);
-            dma_window_part<C, NT, 4, 6>(land, a, gn, tid);
-            run_pass<C, 2, +1, 0, XP>(w, tw, lds, tid);
-#pragma unroll
-            for (int m = 0; m < C::P; m++) w[m] = cmul(w[m], H[m]);
-            dma_window_part<C, NT, 6, 8>(land, a, gn, tid);
-            fft_in_regs<C, -1, 0, XP>(w, tw, lds, tid);
-        } else {
-            dma_window_part<C, NT, 0, 8>(land, a, gn, tid);
-            fft_in_regs<C, +1, 0, XP>(w, tw, lds, tid);
-#pragma unroll
-            for (int m = 0; m < C::P; m++) w[m] = cmul(w[m], H[m]);
-            fft_in_regs<C, -1, 0, XP>(w, tw, lds, tid);
-        }
-        store_block<C, false, NT, false, false>(w, a, g, tid);
-        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");           // the next window has landed; this block's 16 stores stay in flight
     }
 }
 
