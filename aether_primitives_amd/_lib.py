@@ -197,6 +197,11 @@ PROTOTYPES = {
     "aeth_resamp_out_count": (sz, [vp, sz]),
     "aeth_resamp_exec": (i32, [vp, vp, vp, sz, vp, sz]),
     "aeth_resamp_prototype": (i32, [sz, sz, sz, vp]),
+    "aeth_nco_word": (u64, [C.c_double]),
+    "aeth_nco_word_at": (u64, [vp, u64]),
+    "aeth_nco_phasor": (i32, [u64, vp]),
+    "aeth_nco_mix": (i32, [vp, vp, u64, vp, vp, sz]),
+    "aeth_nco_tone": (i32, [vp, vp, u64, f32, vp, sz]),
 }
 
 _lib = None

@@ -637,6 +637,59 @@ AETH_API int aeth_resamp_exec(aeth_resamp *resamp, const aeth_cf32 *hist_dev, co
  * the second half mirrors the first bit for bit.  L == 1 gives 1.  A zero size or a null pointer: AETH_E_ARG. */
 AETH_API int aeth_resamp_prototype(size_t up, size_t down, size_t taps_per_phase, float *out_host);
 
+/* ---- numerically controlled oscillator: frequency shift, tone, chirp (no body in the reference) -- */
+/* The multiplication of a stream by e^{j phi(n)}: what brings a channel at an offset to baseband in front of
+ * aeth_resamp_exec, removes a carrier offset behind aeth_corr_search, and makes test tones and sounding chirps on the
+ * device (the reference has no oscillator; its only phasors are the FFT's twiddles).
+ *
+ * An oscillator is three words, each a fraction of a turn scaled by 2^64: `phase`, `step` (turns per sample) and `rate`
+ * (turns per sample per sample).  The phase word of sample n, n a uint64_t stream position, is
+ *     w(n) = phase + n * step + T(n) * rate        (mod 2^64: plain unsigned wrap-around)
+ *     T(n) = n (n - 1) / 2, computed as (n / 2) * (n - 1) for even n and n * ((n - 1) / 2) for odd n
+ * which is exact for every n in [0, 2^64): a float phase accumulator drifts with the stream position, an integer word
+ * cannot.  The instantaneous frequency from sample n to n + 1 is step + n * rate; rate == 0 is the plain shifter.
+ *
+ * The phasor (c, d) of a word is defined bit for bit.  Every operation is f32 and rounded on its own (no contraction):
+ *     t = w >> 32                                   (uint32)
+ *     k = ((t + 0x20000000) >> 30) & 3              (uint32 wrap-around: the nearest quarter turn)
+ *     r = (int32)(t - (k << 30))                    (uint32 wrap-around, reinterpreted: -2^29 <= r < 2^29)
+ *     a = (float)r * K          K = 0x1.921fb6p-30f, the f32 nearest 2 pi / 2^32; int -> float rounds to nearest even
+ *     s = a * a
+ *     ps = (S3 * s + S2) * s + S1          sn = (a * s) * ps + a
+ *     pc = (C3 * s + C2) * s + C1          cs = (1 - 0.5 * s) + (s * s) * pc
+ *     S1, S2, S3 = -1.6666654611e-1, 8.3321608736e-3, -1.9515295891e-4                   (each rounded once to f32)
+ *     C1, C2, C3 = 4.166664568298827e-2, -1.388731625493765e-3, 2.443315711809948e-5
+ *     (c, d) = (cs, sn), (-sn, cs), (-cs, -sn), (sn, -cs)     for k = 0, 1, 2, 3
+ * (the classic single-precision minimax pair on [-pi/4, pi/4]).  The words 0, 2^62, 2^63 and 3 * 2^62 give exactly
+ * (1, 0), (-0, 1), (-1, -0) and (0, -1).  Against exp(2 pi j w / 2^64) in f64 the phasor is within 1.5e-7.
+ *
+ *   mix    out[i].re = x.re * c - x.im * d,  out[i].im = x.re * d + x.im * c,  x = in[i], (c, d) the phasor of w(n0 + i):
+ *          aeth_vec_mul's expression with the phasor as the second operand
+ *   tone   out[i] = (amp * c, amp * d)
+ * Each output depends only on in[i] and the words: a stream cut anywhere and continued with n0 advanced by the cut gives
+ * the same bits.
+ *
+ * aeth_nco_mix and aeth_nco_tone are ordered on the context's in-order stream like the element-wise calls and validate
+ * everything before any device work: NULL ctx, words or pointers AETH_E_ARG (n == 0 returns AETH_OK without a launch
+ * once ctx and words are there, as for aeth_seq_*); pointers 8-byte aligned (AETH_E_ALIGN); n0 > UINT64_MAX - n
+ * AETH_E_UNSUPPORTED, the message naming both numbers; 2^31 workgroups or more AETH_E_UNSUPPORTED; out_dev == in_dev runs
+ * in place, any other overlap of the two ranges AETH_E_ARG. */
+typedef struct aeth_nco_words { uint64_t phase, step, rate; } aeth_nco_words;
+/* No body in the reference.  Host only: the word of `cycles` turns (or turns per sample).  With x = cycles -
+ * floor(cycles) in f64 it is x * 2^64 truncated toward zero; 0 when x rounds to 1.0 and for NaN or +-Inf.  A negative
+ * frequency is its two's complement: aeth_nco_word(-0.25) == 3 * 2^62. */
+AETH_API uint64_t aeth_nco_word(double cycles);
+/* No body in the reference.  Host only: w(n) as defined above; 0 for a null pointer. */
+AETH_API uint64_t aeth_nco_word_at(const aeth_nco_words *w, uint64_t n);
+/* No body in the reference.  Host only: the phasor of one word, by the same text the kernels run.  out_host NULL:
+ * AETH_E_ARG. */
+AETH_API int aeth_nco_phasor(uint64_t word, aeth_cf32 *out_host);
+/* No body in the reference: the mix as defined above, 8 B read and 8 B written per sample. */
+AETH_API int aeth_nco_mix(aeth_ctx *ctx, const aeth_nco_words *w, uint64_t n0, const aeth_cf32 *in_dev, aeth_cf32 *out_dev,
+                          size_t n);
+/* No body in the reference: the tone (a chirp when rate != 0) as defined above, 8 B written per sample. */
+AETH_API int aeth_nco_tone(aeth_ctx *ctx, const aeth_nco_words *w, uint64_t n0, float amp, aeth_cf32 *out_dev, size_t n);
+
 /* ---- pinned host buffers: src/pool.rs:43-221 -------------------------------------------------- */
 /* The reference's object pool ("useful for large buffers and other time expensive objects", :9-10) with pinned
  * (hipHostMalloc) elements of elem_bytes each: the maker allocates one element, the resetter optionally zeroes it.

@@ -589,6 +589,53 @@ private:
     aeth_resamp *h_ = nullptr;
 };
 
+// ---- numerically controlled oscillator (no body in the reference: it has no frequency shift, tone or chirp) ----------
+// Three 64-bit words, fractions of a turn scaled by 2^64: w(n) = phase + n * step + n (n - 1) / 2 * rate modulo 2^64, exact
+// at every stream position.  mix multiplies by the phasor of w(position + i), tone writes amp times it; both advance
+// `position` by the samples they handled, so the chunks of a stream concatenate bit for bit.
+class Nco {
+public:
+    // freq in cycles per sample, phase in cycles, rate in cycles per sample per sample
+    explicit Nco(Context &ctx, double freq = 0.0, double phase = 0.0, double rate = 0.0, uint64_t position = 0)
+        : ctx_(ctx.get()), w_{aeth_nco_word(phase), aeth_nco_word(freq), aeth_nco_word(rate)}, position_(position) {}
+    static Nco from_words(Context &ctx, uint64_t phase, uint64_t step, uint64_t rate, uint64_t position = 0)
+    {
+        Nco o(ctx);
+        o.w_ = aeth_nco_words{phase, step, rate};
+        o.position_ = position;
+        return o;
+    }
+    static uint64_t word(double cycles) { return aeth_nco_word(cycles); }
+    static uint64_t word_at(const aeth_nco_words &w, uint64_t n) { return aeth_nco_word_at(&w, n); }
+    static aeth_cf32 phasor(uint64_t word)
+    {
+        aeth_cf32 out;
+        check(aeth_nco_phasor(word, &out));
+        return out;
+    }
+    const aeth_nco_words &words() const { return w_; }
+    uint64_t position() const { return position_; }
+    void seek(uint64_t position) { position_ = position; }
+    // out may be x itself (in place)
+    void mix(const DeviceVec &x, DeviceVec &out)
+    {
+        if (x.len() != out.len()) throw Panic(AETH_E_LEN, "Nco::mix: the output's length is not the input's");
+        check(aeth_nco_mix(ctx_, &w_, position_, x.ptr(), out.ptr(), x.len()));
+        position_ += x.len();
+    }
+    void mix(DeviceVec &x) { mix(x, x); }
+    void tone(DeviceVec &out, float amp = 1.0f)
+    {
+        check(aeth_nco_tone(ctx_, &w_, position_, amp, out.ptr(), out.len()));
+        position_ += out.len();
+    }
+
+private:
+    aeth_ctx *ctx_;
+    aeth_nco_words w_;
+    uint64_t position_;
+};
+
 // ---- sequence::expand / sequence::generate for linear generators (src/sequence.rs:18-53) ----------------------------
 // A register is the set of its delays: seq[n] = XOR seq[n - d]; 1 .. 4 registers XORed (Gold codes: two).  `init` holds
 // one word per register, bit i = seq[i] (what expand() unpacks).  Device pointers in and out; bits are one byte each.

@@ -36,6 +36,10 @@ pub struct aeth_corr_peak { pub index: usize, pub norm: c_float, pub n_nan: c_ui
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct aeth_seq_reg { pub delays: *const u32, pub ndelays: usize }
+/// aeth_nco_words: an oscillator, each word a fraction of a turn scaled by 2^64; w(n) = phase + n step + n (n - 1) / 2 rate
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct aeth_nco_words { pub phase: u64, pub step: u64, pub rate: u64 }
 pub const AETH_CHAN_PHASE_FRAME: c_int = 0; pub const AETH_CHAN_PHASE_STREAM: c_int = 1;
 pub const AETH_CHAN_PROTO_RECT: c_int = 0; pub const AETH_CHAN_PROTO_HANN: c_int = 1; pub const AETH_CHAN_PROTO_HAMMING: c_int = 2;
 pub const AETH_CHAN_PROTO_SINC_HAMMING: c_int = 3;
@@ -230,6 +234,11 @@ extern "C" {
     pub fn aeth_resamp_exec(resamp: *mut aeth_resamp, hist_dev: *const cf32, in_dev: *const cf32, n: usize, out_dev: *mut cf32,
                             n_out: usize) -> c_int;
     pub fn aeth_resamp_prototype(up: usize, down: usize, taps_per_phase: usize, out_host: *mut c_float) -> c_int;
+    pub fn aeth_nco_word(cycles: f64) -> u64;
+    pub fn aeth_nco_word_at(w: *const aeth_nco_words, n: u64) -> u64;
+    pub fn aeth_nco_phasor(word: u64, out_host: *mut cf32) -> c_int;
+    pub fn aeth_nco_mix(ctx: *mut aeth_ctx, w: *const aeth_nco_words, n0: u64, in_dev: *const cf32, out_dev: *mut cf32, n: usize) -> c_int;
+    pub fn aeth_nco_tone(ctx: *mut aeth_ctx, w: *const aeth_nco_words, n0: u64, amp: c_float, out_dev: *mut cf32, n: usize) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;

@@ -369,6 +369,39 @@ impl<'c> Resampler<'c> {
 }
 impl<'c> Drop for Resampler<'c> { fn drop(&mut self) { unsafe { aeth_resamp_destroy(self.h); } } }
 
+/// Numerically controlled oscillator (no body in the reference: it has no frequency shift, tone or chirp).  Three 64-bit
+/// words, fractions of a turn scaled by 2^64: w(n) = phase + n * step + n (n - 1) / 2 * rate modulo 2^64, exact at every
+/// stream position.  `mix` and `tone` advance `position` by the samples they handled: chunks concatenate bit for bit.
+pub struct Nco<'c> { ctx: &'c Context, pub words: aeth_nco_words, pub position: u64 }
+impl<'c> Nco<'c> {
+    /// `freq` in cycles per sample, `phase` in cycles, `rate` in cycles per sample per sample
+    pub fn new(ctx: &'c Context, freq: f64, phase: f64, rate: f64, position: u64) -> Nco<'c> {
+        Nco { ctx, words: aeth_nco_words { phase: Nco::word(phase), step: Nco::word(freq), rate: Nco::word(rate) }, position }
+    }
+    pub fn from_words(ctx: &'c Context, words: aeth_nco_words, position: u64) -> Nco<'c> { Nco { ctx, words, position } }
+    pub fn word(cycles: f64) -> u64 { unsafe { aeth_nco_word(cycles) } }
+    pub fn word_at(words: &aeth_nco_words, n: u64) -> u64 { unsafe { aeth_nco_word_at(words, n) } }
+    pub fn phasor(word: u64) -> cf32 {
+        let mut out = cf32::new(0.0, 0.0);
+        check(unsafe { aeth_nco_phasor(word, &mut out) });
+        out
+    }
+    pub fn seek(&mut self, position: u64) { self.position = position; }
+    pub fn mix(&mut self, x: &DeviceVec, out: &mut DeviceVec) {
+        assert_eq!(x.n, out.n, "Nco::mix: the output's length is not the input's");
+        check(unsafe { aeth_nco_mix(self.ctx.h, &self.words, self.position, x.p, out.p, x.n) });
+        self.position += x.n as u64;
+    }
+    pub fn mix_in_place(&mut self, x: &mut DeviceVec) {
+        check(unsafe { aeth_nco_mix(self.ctx.h, &self.words, self.position, x.p, x.p, x.n) });
+        self.position += x.n as u64;
+    }
+    pub fn tone(&mut self, amp: f32, out: &mut DeviceVec) {
+        check(unsafe { aeth_nco_tone(self.ctx.h, &self.words, self.position, amp, out.p, out.n) });
+        self.position += out.n as u64;
+    }
+}
+
 /// The device counterpart of `pipeline::new().add_stage(..)` (src/pipeline.rs:24-41, :123-137): five fixed stages --
 /// copy-in | upload | compute | download | copy-out -- whose compute stage is one of the library's device ops (a closure
 /// cannot cross the C ABI).  `run` takes host slices and returns what `aeth_stream_host` reports.
