@@ -106,6 +106,20 @@ def test_the_truth_helpers_agree_with_each_other(delays):
     assert (seq_truth.block(delays, 0, 66000, state=state) == a[5000:71000]).all()
 
 
+def test_the_truth_is_right_where_the_long_device_call_is_compared():
+    """tests/test_gpu_sequence_long.py compares slices of a 2^30-position call around the starts of chunks 2^j
+    (C = 16384 positions each) with seq_truth.truth, which there goes through py_window and block(state=...): the same
+    route against the period of the order-7 register, which uses neither"""
+    regs, inits, ch, n = ((6, 7),), (0x7f,), 16384, 4160
+    period = seq_truth.m_sequence_bits()
+    tiled = np.tile(period, n // 127 + 2)
+    for skip in (0, 1600, 2 ** 40 + 12345):
+        for j in range(18):
+            for p in ((ch << j) - 64, ch << j, ((1 << j) - 1) * ch + 4096):
+                got = seq_truth.truth(regs, inits, skip + p, n)
+                assert (got == tiled[(skip + p) % 127:][:n]).all(), (skip, j, p)
+
+
 def test_mirror_expand_and_generate_keep_the_reference_quirks():
     assert list(sequence.expand(1 + 4 + 16, 32)) == [1, 0, 1, 0, 1] + [0] * 27                    # sequence.rs:8-16
     with pytest.raises(OverflowError):
