@@ -28,6 +28,8 @@ from . import synth                                       # noqa: E402
 from .synth import Synthesizer                            # noqa: E402
 from . import resamp                                      # noqa: E402
 from .resamp import Resampler                             # noqa: E402
+from . import arb                                         # noqa: E402
+from .arb import ArbResampler, step_word                  # noqa: E402
 from . import nco                                         # noqa: E402
 from .nco import Nco                                      # noqa: E402
 from . import file                                        # noqa: E402
@@ -38,5 +40,6 @@ from .evm import assert_evm, evm_db                       # noqa: E402
 __all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "DeviceF32", "HostVec", "VecStats", "LEVEL_NORM",
            "LEVEL_DB", "LEVEL_POWER_DB", "Scale", "HipFft",
            "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "Corr", "CorrPeak", "sampling", "modulation", "noise", "sequence", "Sequence",
-           "lte_gold", "chan", "Channelizer", "synth", "Synthesizer", "resamp", "Resampler", "nco", "Nco",
+           "lte_gold", "chan", "Channelizer", "synth", "Synthesizer", "resamp", "Resampler", "arb", "ArbResampler", "step_word",
+           "nco", "Nco",
            "assert_evm", "evm_db"]

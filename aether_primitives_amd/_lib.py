@@ -197,6 +197,15 @@ PROTOTYPES = {
     "aeth_resamp_out_count": (sz, [vp, sz]),
     "aeth_resamp_exec": (i32, [vp, vp, vp, sz, vp, sz]),
     "aeth_resamp_prototype": (i32, [sz, sz, sz, vp]),
+    "aeth_arb_advance": (i32, [u64, u64, sz, vp, vp]),
+    "aeth_arb_create": (i32, [vp, vp, sz, sz, pvp]),
+    "aeth_arb_destroy": (i32, [vp]),
+    "aeth_arb_phases": (sz, [vp]),
+    "aeth_arb_ntaps": (sz, [vp]),
+    "aeth_arb_history": (sz, [vp]),
+    "aeth_arb_tile": (sz, [vp, u64]),
+    "aeth_arb_route": (C.c_char_p, [vp, u64]),
+    "aeth_arb_exec": (i32, [vp, vp, vp, sz, u64, u64, vp, sz]),
     "aeth_nco_word": (u64, [C.c_double]),
     "aeth_nco_word_at": (u64, [vp, u64]),
     "aeth_nco_phasor": (i32, [u64, vp]),

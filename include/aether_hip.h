@@ -53,6 +53,7 @@ typedef struct aeth_seq aeth_seq;       /* LFSR sequences: sequence::generate (s
 typedef struct aeth_chan aeth_chan;     /* polyphase analysis filter bank: windowed, overlapped frames in front of aeth_fft */
 typedef struct aeth_synth aeth_synth;   /* polyphase synthesis filter bank: weighted overlap-add behind aeth_fft */
 typedef struct aeth_resamp aeth_resamp; /* polyphase rational resampler: up U, real FIR, down Q in one pass */
+typedef struct aeth_arb aeth_arb;       /* arbitrary-ratio resampler: interpolated polyphase taps behind a Q32.32 time word */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -636,6 +637,81 @@ AETH_API int aeth_resamp_exec(aeth_resamp *resamp, const aeth_cf32 *hist_dev, co
  * scaled so that the taps sum to `up` (unit passband gain after zero stuffing), computed in f64 and rounded once to f32;
  * the second half mirrors the first bit for bit.  L == 1 gives 1.  A zero size or a null pointer: AETH_E_ARG. */
 AETH_API int aeth_resamp_prototype(size_t up, size_t down, size_t taps_per_phase, float *out_host);
+
+/* ---- arbitrary-ratio resampler: integer time word, interpolated taps (no body in the reference) -- */
+/* A stream converted by a ratio that is no small fraction: a sample clock some parts per million off, a symbol rate that
+ * is no simple fraction of the capture rate, 48 kHz to 44.1 kHz * (1 + 20 ppm).  A polyphase bank of L = 2^b phases whose
+ * taps are linearly interpolated between neighbouring phases, addressed by a 64-bit fixed-point time word (the
+ * reference's rate changes, src/sampling.rs:7-62, are linear interpolation and sample picking).
+ *
+ * Object.  An aeth_arb is made of a REAL prototype h[0 .. T) (host floats, copied): T = ntaps = P * L, L = 2^b,
+ * b = log2_phases in 0 .. 12, P in 1 .. 64.  h[T] := +0.0, so the continuous impulse response ends at zero, and
+ *     d[j] = fl32(h[j + 1] - h[j])    for j = 0 .. T - 1
+ * computed on the host in f32 and rounded once.  aeth_resamp_prototype(L, down, P) designs a suitable low-pass; for a
+ * decimating ratio take down = ceil(L * step).
+ *
+ * Time word.  Time is unsigned Q32.32 in a uint64_t: the top 32 bits are the input sample index relative to the call's
+ * first sample, the low 32 bits the fraction.  Output m of a call sits at t(m) = phase + m * step, `step` being the input
+ * samples per output sample, in [2^20, 2^44]: 1/4096 to 4096.  step and phase are arguments of a call, not part of the
+ * object: a tracking loop may change step between chunks.
+ *
+ * The stream, as for aeth_resamp: s[i] = in_dev[i] for 0 <= i < n; for -(P - 1) <= i < 0 it is hist_dev[P - 1 + i].  When
+ * hist_dev is NULL those samples are +0.0, multiplied like any others.  hist_dev is ignored when P == 1.
+ *
+ * Output count and next phase.  A call over n inputs makes every output whose newest sample is inside the call: all
+ * m >= 0 with t(m) < n * 2^32.
+ *     count = 0 if phase >= n * 2^32, else ceil((n * 2^32 - phase) / step)
+ *     next phase = phase + count * step - n * 2^32
+ * Both come from aeth_arb_advance.  n == 0 is a valid call that makes nothing.
+ *
+ * The sample is defined bit for bit.  Every operation is f32 and rounded on its own (no contraction).  For output m:
+ *     a = t >> 32        f = (uint32)t        r = b ? f >> (32 - b) : 0
+ *     mu24 = ((uint32)(f << b)) >> 8          mu = (float)mu24 * 2^-24           (exact)
+ *     j_p = p * L + r
+ *     c_p = h[j_p] + mu * d[j_p]                                      (the product rounded, then the sum rounded)
+ *     out[m] = sum over p = 0 .. P - 1, ascending, of  c_p * s[a - p]
+ * every product rounded, the sum started from the p = 0 product (not from +0), products added left to right, re and im
+ * independently, each as a real multiplication by c_p.  a <= n - 1 always holds, so every output is complete within its
+ * call: chunks cut anywhere concatenate bit for bit when the caller passes the previous P - 1 input samples as history
+ * and the phase from aeth_arb_advance.  With step = Q * 2^32 / L exact and phase 0, mu is always 0 and the values are
+ * those of aeth_resamp_exec with (up = L, down = Q) and the same taps (a tap of -0.0 becomes +0.0).
+ *
+ * aeth_arb_exec is ordered on the context's in-order stream and validates everything before any device work: NULL
+ * pointers AETH_E_ARG; step, phase or n that aeth_arb_advance refuses AETH_E_UNSUPPORTED; n_out other than count
+ * AETH_E_LEN; pointers 8-byte aligned (AETH_E_ALIGN); the output range clear of the input and the history (AETH_E_ARG);
+ * 2^31 workgroups or more AETH_E_UNSUPPORTED.  n_out == 0 in a valid call returns AETH_OK without a launch: a short chunk
+ * under strong decimation legitimately makes nothing. */
+/* No body in the reference (src/sampling.rs:7-62 has no time word).  Host only, needs no context: count and next phase
+ * as defined above, in unsigned 128-bit arithmetic.  AETH_E_UNSUPPORTED, the message naming the number: step outside
+ * [2^20, 2^44]; phase >= 2^63; n > 2^31; any intermediate of 2^64 or more (none is left once the first three hold).  A
+ * null result pointer: AETH_E_ARG.  Nothing is written when the call is refused. */
+AETH_API int aeth_arb_advance(uint64_t step, uint64_t phase, size_t n, size_t *count, uint64_t *next_phase);
+/* No body in the reference (src/sampling.rs:7-62 has only linear interpolation and sample picking).  NULL pointers,
+ * ntaps == 0 or ntaps not a multiple of 2^log2_phases: AETH_E_ARG; log2_phases > 12 or P > 64: AETH_E_UNSUPPORTED; the
+ * message names the offending number, every check comes before the context is used, and nothing stays allocated. */
+AETH_API int aeth_arb_create(aeth_ctx *ctx, const float *taps_host, size_t ntaps, size_t log2_phases, aeth_arb **out);
+/* No body in the reference (src/sampling.rs:7-62 resamples without an object).  Waits for the context's stream. */
+AETH_API int aeth_arb_destroy(aeth_arb *arb);
+/* No body in the reference (src/sampling.rs:7-62: the factor is an argument there): L and T; 0 for a null handle. */
+AETH_API size_t aeth_arb_phases(const aeth_arb *arb);
+AETH_API size_t aeth_arb_ntaps(const aeth_arb *arb);
+/* No body in the reference (src/sampling.rs:7-62 keeps no state between calls): P - 1, the input samples of history a
+ * call reads. */
+AETH_API size_t aeth_arb_history(const aeth_arb *arb);
+/* No body in the reference (src/sampling.rs:7-62): consecutive outputs one workgroup makes at this step, like
+ * aeth_resamp_tile: the largest multiple of 256, at most 4096, with floor((2^32 - 1 + (tile - 1) * step) / 2^32) + P <=
+ * 4096 samples, so that a tile's input span fits 32 KiB of LDS whatever the fraction of its first output is; 256 on the
+ * direct route.  0 for a null handle or a step out of range. */
+AETH_API size_t aeth_arb_tile(const aeth_arb *arb, uint64_t step);
+/* No body in the reference (src/sampling.rs:7-62 has one loop): the kernel route at this step, static text: "staged" (the
+ * inputs of a tile of outputs go through LDS once), followed by " tab" when the tap table, L rows of ceil(P / 2) 16-byte
+ * slots, is at most 512 slots and lies in LDS as well, or "direct" (not even 256 outputs fit the span, which includes
+ * every step that skips inputs: each output reads its own P samples).  "" for a null handle or a step out of range. */
+AETH_API const char *aeth_arb_route(const aeth_arb *arb, uint64_t step);
+/* No body in the reference (src/sampling.rs:7-62 has only linear interpolation and sample picking): the resampler as
+ * defined above.  8 n bytes read and 8 n_out written when every input comes from HBM once. */
+AETH_API int aeth_arb_exec(aeth_arb *arb, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n, uint64_t step,
+                           uint64_t phase, aeth_cf32 *out_dev, size_t n_out);
 
 /* ---- numerically controlled oscillator: frequency shift, tone, chirp (no body in the reference) -- */
 /* The multiplication of a stream by e^{j phi(n)}: what brings a channel at an offset to baseband in front of

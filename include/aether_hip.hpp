@@ -589,6 +589,44 @@ private:
     aeth_resamp *h_ = nullptr;
 };
 
+// ---- arbitrary-ratio resampler (no body in the reference: src/sampling.rs:7-62 interpolates linearly and picks) -------
+// A bank of 2^log2_phases phases whose taps are interpolated linearly between neighbours, behind an unsigned Q32.32 time
+// word: output m of a call stands at phase + m * step input samples.  advance() gives a call's output count and the next
+// call's phase; with the previous history() input samples the chunks of a stream concatenate exactly.
+class ArbResampler {
+public:
+    ArbResampler(Context &ctx, const std::vector<float> &taps, size_t log2_phases)
+    {
+        check(aeth_arb_create(ctx.get(), taps.data(), taps.size(), log2_phases, &h_));
+    }
+    ~ArbResampler() { aeth_arb_destroy(h_); }
+    ArbResampler(const ArbResampler &) = delete;
+    ArbResampler &operator=(const ArbResampler &) = delete;
+    // the Q32.32 word of `ratio` input samples per output sample, truncated
+    static uint64_t step_word(double ratio) { return (uint64_t)(ratio * 4294967296.0); }
+    // outputs of a call over n input samples from `phase`; *next_phase: the phase of the call behind it
+    static size_t advance(uint64_t step, uint64_t phase, size_t n, uint64_t *next_phase)
+    {
+        size_t count = 0;
+        check(aeth_arb_advance(step, phase, n, &count, next_phase));
+        return count;
+    }
+    size_t phases() const { return aeth_arb_phases(h_); }
+    size_t ntaps() const { return aeth_arb_ntaps(h_); }
+    size_t history() const { return aeth_arb_history(h_); }
+    size_t tile(uint64_t step) const { return aeth_arb_tile(h_, step); }
+    std::string route(uint64_t step) const { return aeth_arb_route(h_, step); }
+    // `hist`: the history() samples in front of `x` (null: zeros); out.len() must be advance(step, phase, x.len())
+    void exec(const DeviceVec &x, uint64_t step, uint64_t phase, DeviceVec &out, const DeviceVec *hist = nullptr)
+    {
+        check(aeth_arb_exec(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), step, phase, out.ptr(), out.len()));
+    }
+    aeth_arb *get() const { return h_; }
+
+private:
+    aeth_arb *h_ = nullptr;
+};
+
 // ---- numerically controlled oscillator (no body in the reference: it has no frequency shift, tone or chirp) ----------
 // Three 64-bit words, fractions of a turn scaled by 2^64: w(n) = phase + n * step + n (n - 1) / 2 * rate modulo 2^64, exact
 // at every stream position.  mix multiplies by the phasor of w(position + i), tone writes amp times it; both advance

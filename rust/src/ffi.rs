@@ -11,6 +11,7 @@ use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_chan { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_synth { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_resamp { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_arb { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
 pub const AETH_POOL_ZERO_ON_RETURN: c_int = 1;
@@ -234,6 +235,17 @@ extern "C" {
     pub fn aeth_resamp_exec(resamp: *mut aeth_resamp, hist_dev: *const cf32, in_dev: *const cf32, n: usize, out_dev: *mut cf32,
                             n_out: usize) -> c_int;
     pub fn aeth_resamp_prototype(up: usize, down: usize, taps_per_phase: usize, out_host: *mut c_float) -> c_int;
+    pub fn aeth_arb_advance(step: u64, phase: u64, n: usize, count: *mut usize, next_phase: *mut u64) -> c_int;
+    pub fn aeth_arb_create(ctx: *mut aeth_ctx, taps_host: *const c_float, ntaps: usize, log2_phases: usize,
+                           out: *mut *mut aeth_arb) -> c_int;
+    pub fn aeth_arb_destroy(arb: *mut aeth_arb) -> c_int;
+    pub fn aeth_arb_phases(arb: *const aeth_arb) -> usize;
+    pub fn aeth_arb_ntaps(arb: *const aeth_arb) -> usize;
+    pub fn aeth_arb_history(arb: *const aeth_arb) -> usize;
+    pub fn aeth_arb_tile(arb: *const aeth_arb, step: u64) -> usize;
+    pub fn aeth_arb_route(arb: *const aeth_arb, step: u64) -> *const c_char;
+    pub fn aeth_arb_exec(arb: *mut aeth_arb, hist_dev: *const cf32, in_dev: *const cf32, n: usize, step: u64, phase: u64,
+                         out_dev: *mut cf32, n_out: usize) -> c_int;
     pub fn aeth_nco_word(cycles: f64) -> u64;
     pub fn aeth_nco_word_at(w: *const aeth_nco_words, n: u64) -> u64;
     pub fn aeth_nco_phasor(word: u64, out_host: *mut cf32) -> c_int;

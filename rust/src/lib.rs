@@ -369,6 +369,38 @@ impl<'c> Resampler<'c> {
 }
 impl<'c> Drop for Resampler<'c> { fn drop(&mut self) { unsafe { aeth_resamp_destroy(self.h); } } }
 
+/// Arbitrary-ratio resampler (no body in the reference: src/sampling.rs:7-62 has only linear interpolation and sample
+/// picking): 2^log2_phases phases whose taps are interpolated linearly between neighbours, behind an unsigned Q32.32 time
+/// word.  Output m of a call stands at phase + m * step input samples; `advance` gives a call's output count and the next
+/// call's phase, and the previous `history()` input samples make chunks concatenate exactly.
+pub struct ArbResampler<'c> { h: *mut aeth_arb, _ctx: PhantomData<&'c Context> }
+impl<'c> ArbResampler<'c> {
+    pub fn new(ctx: &'c Context, taps: &[f32], log2_phases: usize) -> ArbResampler<'c> {
+        let mut h = ptr::null_mut();
+        check(unsafe { aeth_arb_create(ctx.h, taps.as_ptr(), taps.len(), log2_phases, &mut h) });
+        ArbResampler { h, _ctx: PhantomData }
+    }
+    /// the Q32.32 word of `ratio` input samples per output sample, truncated
+    pub fn step_word(ratio: f64) -> u64 { (ratio * 4294967296.0) as u64 }
+    /// (outputs of a call over n input samples from `phase`, the phase of the call behind it)
+    pub fn advance(step: u64, phase: u64, n: usize) -> (usize, u64) {
+        let (mut count, mut next) = (0usize, 0u64);
+        check(unsafe { aeth_arb_advance(step, phase, n, &mut count, &mut next) });
+        (count, next)
+    }
+    pub fn phases(&self) -> usize { unsafe { aeth_arb_phases(self.h) } }
+    pub fn ntaps(&self) -> usize { unsafe { aeth_arb_ntaps(self.h) } }
+    /// input samples in front of a call's first that reach into its output: taps per phase - 1
+    pub fn history(&self) -> usize { unsafe { aeth_arb_history(self.h) } }
+    pub fn tile(&self, step: u64) -> usize { unsafe { aeth_arb_tile(self.h, step) } }
+    pub fn route(&self, step: u64) -> String { unsafe { std::ffi::CStr::from_ptr(aeth_arb_route(self.h, step)) }.to_string_lossy().into_owned() }
+    /// `hist`: the history() samples in front of `x` (None: zeros); `out` holds advance(step, phase, x.n).0 samples
+    pub fn exec(&mut self, x: &DeviceVec, step: u64, phase: u64, hist: Option<&DeviceVec>, out: &mut DeviceVec) {
+        check(unsafe { aeth_arb_exec(self.h, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n, step, phase, out.p, out.n) });
+    }
+}
+impl<'c> Drop for ArbResampler<'c> { fn drop(&mut self) { unsafe { aeth_arb_destroy(self.h); } } }
+
 /// Numerically controlled oscillator (no body in the reference: it has no frequency shift, tone or chirp).  Three 64-bit
 /// words, fractions of a turn scaled by 2^64: w(n) = phase + n * step + n (n - 1) / 2 * rate modulo 2^64, exact at every
 /// stream position.  `mix` and `tone` advance `position` by the samples they handled: chunks concatenate bit for bit.
