@@ -134,6 +134,7 @@ PROTOTYPES = {
     "aeth_modulate": (i32, [vp, vp, sz, i32, vp, vp, sz]),
     "aeth_modulate_awgn": (i32, [vp, vp, sz, i32, vp, vp, sz, f32, C.c_uint64, C.c_uint64]),
     "aeth_demod_naive": (i32, [vp, vp, sz, i32, vp, vp, sz, i32]),
+    "aeth_demod_soft": (i32, [vp, vp, sz, i32, vp, f32, vp, sz]),
     "aeth_awgn_apply": (i32, [vp, vp, sz, f32, C.c_uint64, C.c_uint64]),
     "aeth_awgn_fill": (i32, [vp, vp, sz, f32, C.c_uint64, C.c_uint64]),
     "aeth_rng_philox4x32_10": (i32, [vp, vp, sz, vp]),
@@ -211,6 +212,16 @@ PROTOTYPES = {
     "aeth_nco_phasor": (i32, [u64, vp]),
     "aeth_nco_mix": (i32, [vp, vp, u64, vp, vp, sz]),
     "aeth_nco_tone": (i32, [vp, vp, u64, f32, vp, sz]),
+    "aeth_cc_create": (i32, [vp, vp, sz, sz, sz, pvp]),
+    "aeth_cc_destroy": (i32, [vp]),
+    "aeth_cc_k": (sz, [vp]),
+    "aeth_cc_n": (sz, [vp]),
+    "aeth_cc_block": (sz, [vp]),
+    "aeth_cc_warmup": (sz, [vp]),
+    "aeth_cc_traceback": (sz, [vp]),
+    "aeth_cc_history": (sz, [vp]),
+    "aeth_cc_encode": (i32, [vp, vp, vp, sz, vp, sz]),
+    "aeth_cc_decode": (i32, [vp, vp, vp, sz, vp, sz]),
 }
 
 _lib = None

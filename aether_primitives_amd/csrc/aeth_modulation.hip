@@ -177,6 +177,56 @@ __global__ __launch_bounds__(kBlock) void demod_generic_kernel(const float2 *__r
     for (int k = 0; k < bps; k++) bits[i * (size_t)bps + k] = (uint8_t)((best >> k) & 1u);      // :143
 }
 
+// ---- soft demodulation (no body in the reference; definition in include/aether_hip.h, aeth_demod_soft): per bit of
+// the index the difference of the two nearest squared distances, scaled, rounded and clamped to int8.  One lane per
+// symbol, the table in LDS, the 2 * BPS running minima in registers; the candidate loop is wave-uniform.
+template <int BPS, bool NT>
+__global__ __launch_bounds__(kBlock) void demod_soft_kernel(const float2 *__restrict__ sym, int8_t *__restrict__ out, size_t nsym,
+                                                            float scale, int wide, TableN t)
+{
+    constexpr int NC = 1 << BPS;
+    __shared__ float2 tab[NC];
+    for (int k = threadIdx.x; k < NC; k += kBlock) tab[k] = t.s[k];
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nsym) return;
+    const float2 v = aeth::nt_load<NT>(sym + i);
+    float b0[BPS], b1[BPS];
+#pragma unroll
+    for (int k = 0; k < BPS; k++) b0[k] = b1[k] = __builtin_inff();
+    for (int c = 0; c < NC; c++) {
+        const float dr = v.x - tab[c].x, di = v.y - tab[c].y;
+        const float d = dr * dr + di * di;
+#pragma unroll
+        for (int k = 0; k < BPS; k++) {
+            if ((c >> k) & 1) b1[k] = d < b1[k] ? d : b1[k];
+            else b0[k] = d < b0[k] ? d : b0[k];
+        }
+    }
+    uint8_t q[BPS];
+#pragma unroll
+    for (int k = 0; k < BPS; k++) {
+        const float l = (b1[k] - b0[k]) * scale;
+        float r = rintf(l);
+        r = r < -127.f ? -127.f : (r > 127.f ? 127.f : r);
+        q[k] = l != l ? (uint8_t)0 : (uint8_t)(int8_t)(int)r;
+    }
+    // a symbol's BPS bytes in one store where BPS is a power of two and `out` is aligned to it (`wide`)
+    if constexpr (BPS == 2) {
+        if (wide) { reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)(q[0] | (q[1] << 8)); return; }
+    } else if constexpr (BPS == 4 || BPS == 8) {
+        if (wide) {
+#pragma unroll
+            for (int w = 0; w < BPS / 4; w++)
+                reinterpret_cast<uint32_t *>(out)[i * (BPS / 4) + w] =
+                    (uint32_t)q[4 * w] | ((uint32_t)q[4 * w + 1] << 8) | ((uint32_t)q[4 * w + 2] << 16) | ((uint32_t)q[4 * w + 3] << 24);
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < BPS; k++) out[i * BPS + k] = (int8_t)q[k];
+}
+
 // modulate, then Awgn::apply on the fresh symbols (examples/modem.rs:19-26: `let mut tx = qpsk().modulate(&bits);
 // awgn.apply(&mut tx)`) in one pass: the symbol never goes to memory without its noise.  One lane per PAIR of
 // symbols = one Philox call; arithmetic exactly that of modulate_kernel + awgn_apply_kernel (noise.rs:41-42,58).
@@ -375,6 +425,40 @@ int aeth_demod_naive(aeth_ctx *ctx, const aeth_cf32 *sym, size_t nsym, int bps, 
     else if (vec)        AETH_DEM(2, true, gv);
     else                 AETH_DEM(2, false, gs);
 #undef AETH_DEM
+    AETH_HIP(hipGetLastError());
+    return AETH_OK;
+}
+
+int aeth_demod_soft(aeth_ctx *ctx, const aeth_cf32 *sym, size_t nsym, int bps, const aeth_cf32 *table, float scale, int8_t *out,
+                    size_t nout)
+{
+    AETH_REQUIRE(ctx, AETH_E_ARG, "ctx is null");
+    AETH_REQUIRE(bps >= 1 && bps <= 8, AETH_E_UNSUPPORTED, "bits_per_symbol %d: 1 .. 8 supported", bps);
+    TableN tn;
+    if (bps > 2) { int rc = fill_table_n(tn, bps, table); if (rc) return rc; }
+    else {
+        for (int i = 0; i < 256; i++) tn.s[i] = make_float2(0.f, 0.f);
+        for (int i = 0; i < (1 << bps); i++)
+            tn.s[i] = table ? make_float2(table[i].re, table[i].im) : (bps == 1 ? kBpsk[i] : kQpsk[i]);
+    }
+    AETH_REQUIRE(nsym <= SIZE_MAX / (size_t)bps && nout == nsym * (size_t)bps, AETH_E_LEN, "output holds %zu values, input gives %zu", nout,
+                 nsym <= SIZE_MAX / (size_t)bps ? nsym * (size_t)bps : (size_t)0);
+    if (nsym == 0) return AETH_OK;
+    AETH_REQUIRE(sym && out, AETH_E_ARG, "null pointer");
+    AETH_REQUIRE(aeth::aligned8(sym), AETH_E_ALIGN, "pointer alignment");
+    AETH_REQUIRE(!aeth::ranges_touch(sym, nsym * sizeof(float2), out, nout), AETH_E_ARG, "the output overlaps the symbols");
+    AETH_REQUIRE((nsym + kBlock - 1) / kBlock < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu symbols need 2^31 workgroups or more", nsym);
+    aeth::DeviceGuard dg(ctx->device);
+    const bool nt = aeth::streams_past_cache(nsym * sizeof(float2));
+    const dim3 g(grid_for(nsym)), b(kBlock);
+    const int wide = ((uintptr_t)out % (size_t)(bps == 8 ? 4 : bps)) == 0 ? 1 : 0;      // only looked at for 2, 4, 8 bits per symbol
+#define AETH_SOFT(B)                                                                                                              \
+    case B:                                                                                                                       \
+        if (nt) hipLaunchKernelGGL((demod_soft_kernel<B, true>), g, b, 0, aeth::ctx_stream(ctx), (const float2 *)sym, out, nsym, scale, wide, tn);  \
+        else hipLaunchKernelGGL((demod_soft_kernel<B, false>), g, b, 0, aeth::ctx_stream(ctx), (const float2 *)sym, out, nsym, scale, wide, tn);    \
+        break
+    switch (bps) { AETH_SOFT(1); AETH_SOFT(2); AETH_SOFT(3); AETH_SOFT(4); AETH_SOFT(5); AETH_SOFT(6); AETH_SOFT(7); AETH_SOFT(8); }
+#undef AETH_SOFT
     AETH_HIP(hipGetLastError());
     return AETH_OK;
 }

@@ -35,6 +35,29 @@ class DeviceBits:
             pass
 
 
+class DeviceSoft:
+    """int8 soft decisions in HBM, one per coded bit: positive means bit 0 is likelier, 0 is an erasure."""
+
+    def __init__(self, ctx, n, host=None):
+        self.ctx, self.n = ctx, int(n)
+        self.ptr = ctx.alloc(max(self.n, 1))
+        if host is not None and self.n:
+            ctx.upload(self.ptr, np.ascontiguousarray(host, np.int8))
+
+    def to_host(self):
+        out = np.empty(self.n, np.int8)
+        if self.n:
+            self.ctx.download(self.ptr, out)
+        return out
+
+    def __del__(self):
+        try:
+            if self.ptr and self.ctx.h:
+                self.ctx.free(self.ptr); self.ptr = None
+        except Exception:
+            pass
+
+
 class _Modulation:
     BITS_PER_SYMBOL = 0
     table = None
@@ -91,6 +114,15 @@ class _Modulation:
         check(self._lib.aeth_demod_naive(self.ctx.h, symbols._p(), symbols.n, self.BITS_PER_SYMBOL,
                                          self.table.ctypes.data_as(C.c_void_p), C.c_void_p(out.ptr), out.n,
                                          1 if compat else 0))
+        return out
+
+    def demod_soft(self, symbols, scale, out=None):             # no body in the reference: aeth_demod_soft
+        """per bit of the index, (nearest squared distance with the bit 1 - with the bit 0) * scale, rounded and clamped
+        to [-127, 127] -> DeviceSoft of BITS_PER_SYMBOL values per symbol"""
+        if out is None:
+            out = DeviceSoft(self.ctx, symbols.n * self.BITS_PER_SYMBOL)
+        check(self._lib.aeth_demod_soft(self.ctx.h, symbols._p(), symbols.n, self.BITS_PER_SYMBOL,
+                                        self.table.ctypes.data_as(C.c_void_p), float(scale), C.c_void_p(out.ptr), out.n))
         return out
 
 

@@ -54,6 +54,7 @@ typedef struct aeth_chan aeth_chan;     /* polyphase analysis filter bank: windo
 typedef struct aeth_synth aeth_synth;   /* polyphase synthesis filter bank: weighted overlap-add behind aeth_fft */
 typedef struct aeth_resamp aeth_resamp; /* polyphase rational resampler: up U, real FIR, down Q in one pass */
 typedef struct aeth_arb aeth_arb;       /* arbitrary-ratio resampler: interpolated polyphase taps behind a Q32.32 time word */
+typedef struct aeth_cc aeth_cc;         /* convolutional code: encoder and block-wise soft-decision Viterbi decoder */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -766,6 +767,56 @@ AETH_API int aeth_nco_mix(aeth_ctx *ctx, const aeth_nco_words *w, uint64_t n0, c
 /* No body in the reference: the tone (a chirp when rate != 0) as defined above, 8 B written per sample. */
 AETH_API int aeth_nco_tone(aeth_ctx *ctx, const aeth_nco_words *w, uint64_t n0, float amp, aeth_cf32 *out_dev, size_t n);
 
+/* ---- convolutional codes: encoder and soft-decision Viterbi decoder (no body in the reference) ---- */
+/* Forward error correction between the bits and the symbols: the rate 1/n codes of constraint length k = 3 .. 7 (the
+ * K = 7 codes of 802.11, DVB-S, CCSDS and LTE have 64 states, one per lane of a wave).  Everything is integer and defined
+ * bit for bit.  Bits are one byte per bit as everywhere in the library.
+ *
+ * The code.  3 <= k <= 7, 2 <= n <= 4, 0 < poly[j] < 2^k in the usual octal convention with the current bit at the MSB
+ * (K = 7: 0171, 0133):
+ *     reg_t = sum_{i < k} u[t - i] * 2^(k - 1 - i)          c[n t + j] = parity(reg_t & poly[j])
+ * u[t] for t < 0 is the caller's history of k - 1 bits (hist[i] = u[i - (k - 1)]), or zero for NULL.  Input bytes are
+ * taken & 1.  Each output needs k input bits and nothing else, so the chunks of a stream concatenate bit for bit when
+ * each call gets the last k - 1 bits of the one before as its history.
+ *
+ * The decoder.  Soft values are int8_t, one per coded bit in the encoder's output order; positive means bit 0 is
+ * likelier, 0 is an erasure (a depunctured stream simply carries zeros).  A call has N = nbits steps; its history is
+ * A + T steps of n values each before step 0, NULL meaning erasures.
+ *   Delay.    out[o] is the decision for step o - T: the decoder is a causal system with delay T.
+ *   Blocks.   Output block b is o in [b D, min(N, (b + 1) D)).  Its window is steps [b D - T - A, min(N, (b + 1) D)).
+ *   Metrics.  Every window starts with all S = 2^(k-1) state metrics at 0, held as int32.  No normalisation is needed:
+ *             |metric| <= 8192 * 4 * 128.
+ *   States.   State s holds u[t-1] at bit k-2 down to u[t-k+1] at bit 0.  Step t enters state j from p0 = (2 j) mod S
+ *             or p1 = p0 + 1 with input bit u = j >> (k-2);
+ *                 cand_d = m[p_d] + sum_q (1 - 2 c_q(u, p_d)) * v[n t + q],
+ *             c_q(u, p) = parity((u 2^(k-1) + p) & poly[q]).  p1 is taken only if cand_1 > cand_0; a tie takes p0.
+ *   Traceback.  At the window's end take the state with the largest metric, ties to the smallest state, and trace
+ *             back, emitting u of every step that maps to an output of the block.  The first A steps of a window store
+ *             no decisions.
+ * Consequences: two calls equal one call, bit for bit, when the first call's N is a multiple of D and the second gets
+ * the first's last A + T steps as history.  A known zero start state is a history of +127s.  A stream is flushed by T
+ * steps of erasures (the first T outputs of a stream are decisions about its history).
+ *
+ * aeth_cc_create: block D >= 1, D + T <= 4096, A <= 4096.  k = 8 and 9 (two and four states per lane) are refused with
+ * AETH_E_UNSUPPORTED, the message naming k; every other violation is AETH_E_ARG naming the offending value.  The object
+ * owns no device memory.  aeth_cc_history is A + T, in trellis steps.
+ * aeth_cc_encode: ncoded != nbits * n is AETH_E_LEN.  aeth_cc_decode: nsoft != nbits * n is AETH_E_LEN.  Pointers may
+ * have any byte alignment; an output range that shares a byte with an input or history range is AETH_E_ARG.  Both are
+ * ordered on the context's stream and validate everything before any device work; a length of 0 launches nothing. */
+typedef struct aeth_cc_code { uint32_t k; uint32_t n; uint32_t poly[4]; } aeth_cc_code;
+AETH_API int aeth_cc_create(aeth_ctx *ctx, const aeth_cc_code *code, size_t block, size_t warmup, size_t traceback, aeth_cc **out);
+AETH_API int aeth_cc_destroy(aeth_cc *cc);
+AETH_API size_t aeth_cc_k(const aeth_cc *cc);
+AETH_API size_t aeth_cc_n(const aeth_cc *cc);
+AETH_API size_t aeth_cc_block(const aeth_cc *cc);
+AETH_API size_t aeth_cc_warmup(const aeth_cc *cc);
+AETH_API size_t aeth_cc_traceback(const aeth_cc *cc);
+AETH_API size_t aeth_cc_history(const aeth_cc *cc);
+AETH_API int aeth_cc_encode(aeth_cc *cc, const uint8_t *hist_bits_dev, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev,
+                            size_t ncoded);
+AETH_API int aeth_cc_decode(aeth_cc *cc, const int8_t *hist_soft_dev, const int8_t *soft_dev, size_t nsoft, uint8_t *bits_dev,
+                            size_t nbits);
+
 /* ---- pinned host buffers: src/pool.rs:43-221 -------------------------------------------------- */
 /* The reference's object pool ("useful for large buffers and other time expensive objects", :9-10) with pinned
  * (hipHostMalloc) elements of elem_bytes each: the maker allocates one element, the resetter optionally zeroes it.
@@ -941,6 +992,14 @@ AETH_API int aeth_modulate_awgn(aeth_ctx *ctx, const uint8_t *bits_dev, size_t n
  * trait default (:133-144).  bits_out_dev receives nsym * bits_per_symbol bytes. */
 AETH_API int aeth_demod_naive(aeth_ctx *ctx, const aeth_cf32 *sym_dev, size_t nsym, int bits_per_symbol,
                               const aeth_cf32 *table_host, uint8_t *bits_out_dev, size_t nbits_out, int compat);
+/* No body in the reference (hence no `compat`): soft decisions for aeth_cc_decode.  bits_per_symbol 1 .. 8 and the tables
+ * of aeth_modulate (NULL: the generic BPSK / QPSK table).  For bit i of the index, at out[bits_per_symbol * s + i]:
+ *     L = (min_{idx: bit i = 1} d2(idx) - min_{idx: bit i = 0} d2(idx)) * scale
+ * with dre = sym.re - table[idx].re, dim likewise, d2 = dre * dre + dim * dim, every operation f32 and rounded on its
+ * own; each minimum starts at +Inf and is a running `d < best ? d : best` over ascending idx.  The output is rintf(L)
+ * clamped to [-127, 127]; NaN gives 0.  Positive means bit 0 is likelier.  nout != nsym * bits_per_symbol: AETH_E_LEN. */
+AETH_API int aeth_demod_soft(aeth_ctx *ctx, const aeth_cf32 *sym_dev, size_t nsym, int bits_per_symbol,
+                             const aeth_cf32 *table_host, float scale, int8_t *out_dev, size_t nout);
 
 /* ---- noise (SURVEY 8f "next" #1): src/noise.rs ------------------------------------- */
 /* Awgn::apply (:53-59) on a device-resident signal: s[i] += next().scale(scale) with

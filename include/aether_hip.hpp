@@ -674,6 +674,45 @@ private:
     uint64_t position_;
 };
 
+// ---- convolutional codes (no body in the reference: it has no forward error correction) ------------------------------
+// A rate 1/n code of constraint length k = 3 .. 7, polynomials in the octal convention with the current bit at the MSB
+// (K = 7: 0171, 0133).  Device pointers in and out; bits are one byte each, soft values int8_t (positive: bit 0 likelier,
+// 0: erasure).  decode is a causal system with a delay of traceback() steps: out[o] is the decision for step o - traceback().
+class ConvCode {
+public:
+    ConvCode(Context &ctx, uint32_t k, const std::vector<uint32_t> &polys, size_t block = 512, size_t warmup = 64, size_t traceback = 64)
+    {
+        if (polys.size() > 4) throw Panic(AETH_E_ARG, "ConvCode: at most 4 polynomials");
+        aeth_cc_code code{k, (uint32_t)polys.size(), {0, 0, 0, 0}};
+        for (size_t i = 0; i < polys.size(); i++) code.poly[i] = polys[i];
+        check(aeth_cc_create(ctx.get(), &code, block, warmup, traceback, &h_));
+    }
+    ~ConvCode() { aeth_cc_destroy(h_); }
+    ConvCode(const ConvCode &) = delete;
+    ConvCode &operator=(const ConvCode &) = delete;
+    size_t k() const { return aeth_cc_k(h_); }
+    size_t n() const { return aeth_cc_n(h_); }
+    size_t block() const { return aeth_cc_block(h_); }
+    size_t warmup() const { return aeth_cc_warmup(h_); }
+    size_t traceback() const { return aeth_cc_traceback(h_); }
+    // warmup + traceback: the steps of soft values a continued decode wants in front
+    size_t history() const { return aeth_cc_history(h_); }
+    // `hist_dev`: the k - 1 bits before bits_dev[0] (null: zeros); coded_dev holds nbits * n bytes
+    void encode(const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded, const uint8_t *hist_dev = nullptr)
+    {
+        check(aeth_cc_encode(h_, hist_dev, bits_dev, nbits, coded_dev, ncoded));
+    }
+    // `hist_dev`: the history() * n soft values before soft_dev[0] (null: erasures); bits_dev holds nsoft / n bytes
+    void decode(const int8_t *soft_dev, size_t nsoft, uint8_t *bits_dev, size_t nbits, const int8_t *hist_dev = nullptr)
+    {
+        check(aeth_cc_decode(h_, hist_dev, soft_dev, nsoft, bits_dev, nbits));
+    }
+    aeth_cc *get() const { return h_; }
+
+private:
+    aeth_cc *h_ = nullptr;
+};
+
 // ---- sequence::expand / sequence::generate for linear generators (src/sequence.rs:18-53) ----------------------------
 // A register is the set of its delays: seq[n] = XOR seq[n - d]; 1 .. 4 registers XORed (Gold codes: two).  `init` holds
 // one word per register, bit i = seq[i] (what expand() unpacks).  Device pointers in and out; bits are one byte each.

@@ -12,6 +12,7 @@ use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_synth { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_resamp { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_arb { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_cc { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
 pub const AETH_POOL_ZERO_ON_RETURN: c_int = 1;
@@ -41,6 +42,10 @@ pub struct aeth_seq_reg { pub delays: *const u32, pub ndelays: usize }
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
 pub struct aeth_nco_words { pub phase: u64, pub step: u64, pub rate: u64 }
+/// aeth_cc_code: a rate 1/n convolutional code of constraint length k; polynomials in the octal convention, current bit at the MSB
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct aeth_cc_code { pub k: u32, pub n: u32, pub poly: [u32; 4] }
 pub const AETH_CHAN_PHASE_FRAME: c_int = 0; pub const AETH_CHAN_PHASE_STREAM: c_int = 1;
 pub const AETH_CHAN_PROTO_RECT: c_int = 0; pub const AETH_CHAN_PROTO_HANN: c_int = 1; pub const AETH_CHAN_PROTO_HAMMING: c_int = 2;
 pub const AETH_CHAN_PROTO_SINC_HAMMING: c_int = 3;
@@ -251,6 +256,19 @@ extern "C" {
     pub fn aeth_nco_phasor(word: u64, out_host: *mut cf32) -> c_int;
     pub fn aeth_nco_mix(ctx: *mut aeth_ctx, w: *const aeth_nco_words, n0: u64, in_dev: *const cf32, out_dev: *mut cf32, n: usize) -> c_int;
     pub fn aeth_nco_tone(ctx: *mut aeth_ctx, w: *const aeth_nco_words, n0: u64, amp: c_float, out_dev: *mut cf32, n: usize) -> c_int;
+    pub fn aeth_cc_create(ctx: *mut aeth_ctx, code: *const aeth_cc_code, block: usize, warmup: usize, traceback: usize,
+                          out: *mut *mut aeth_cc) -> c_int;
+    pub fn aeth_cc_destroy(cc: *mut aeth_cc) -> c_int;
+    pub fn aeth_cc_k(cc: *const aeth_cc) -> usize;
+    pub fn aeth_cc_n(cc: *const aeth_cc) -> usize;
+    pub fn aeth_cc_block(cc: *const aeth_cc) -> usize;
+    pub fn aeth_cc_warmup(cc: *const aeth_cc) -> usize;
+    pub fn aeth_cc_traceback(cc: *const aeth_cc) -> usize;
+    pub fn aeth_cc_history(cc: *const aeth_cc) -> usize;
+    pub fn aeth_cc_encode(cc: *mut aeth_cc, hist_bits_dev: *const u8, bits_dev: *const u8, nbits: usize, coded_dev: *mut u8,
+                          ncoded: usize) -> c_int;
+    pub fn aeth_cc_decode(cc: *mut aeth_cc, hist_soft_dev: *const i8, soft_dev: *const i8, nsoft: usize, bits_dev: *mut u8,
+                          nbits: usize) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;
@@ -302,6 +320,8 @@ extern "C" {
                               n_out: usize, power: c_float, seed: u64, offset: u64) -> c_int;
     pub fn aeth_demod_naive(ctx: *mut aeth_ctx, sym: *const cf32, nsym: usize, bits_per_symbol: c_int,
                             table: *const cf32, bits_out: *mut u8, nbits_out: usize, compat: c_int) -> c_int;
+    pub fn aeth_demod_soft(ctx: *mut aeth_ctx, sym: *const cf32, nsym: usize, bits_per_symbol: c_int, table: *const cf32,
+                           scale: c_float, out: *mut i8, nout: usize) -> c_int;
     pub fn aeth_awgn_apply(ctx: *mut aeth_ctx, signal: *mut cf32, n: usize, power: c_float, seed: u64, offset: u64) -> c_int;
     pub fn aeth_awgn_fill(ctx: *mut aeth_ctx, target: *mut cf32, n: usize, power: c_float, seed: u64, offset: u64) -> c_int;
     pub fn aeth_rng_philox4x32_10(ctx: *mut aeth_ctx, ctr_key: *const u32, n: usize, out: *mut u32) -> c_int;

@@ -434,6 +434,39 @@ impl<'c> Nco<'c> {
     }
 }
 
+/// Convolutional code (no body in the reference: it has no forward error correction): a rate 1/n code of constraint
+/// length k = 3 .. 7, polynomials in the octal convention with the current bit at the MSB (K = 7: 0o171, 0o133).  Bits are
+/// one byte each; soft values are i8, positive meaning bit 0 is likelier, 0 an erasure.  `decode` is a causal system with
+/// a delay of `traceback()` steps: out[o] is the decision for step o - traceback().
+pub struct ConvCode<'c> { h: *mut aeth_cc, _ctx: &'c Context }
+impl<'c> ConvCode<'c> {
+    /// output block `block`, warm-up `warmup` and traceback `traceback` in trellis steps (block + traceback <= 4096)
+    pub fn new(ctx: &'c Context, k: u32, polys: &[u32], block: usize, warmup: usize, traceback: usize) -> ConvCode<'c> {
+        assert!(polys.len() <= 4, "ConvCode::new: at most 4 polynomials");
+        let mut code = aeth_cc_code { k, n: polys.len() as u32, poly: [0; 4] };
+        code.poly[..polys.len()].copy_from_slice(polys);
+        let mut h = ptr::null_mut();
+        check(unsafe { aeth_cc_create(ctx.h, &code, block, warmup, traceback, &mut h) });
+        ConvCode { h, _ctx: ctx }
+    }
+    pub fn k(&self) -> usize { unsafe { aeth_cc_k(self.h) } }
+    pub fn n(&self) -> usize { unsafe { aeth_cc_n(self.h) } }
+    pub fn block(&self) -> usize { unsafe { aeth_cc_block(self.h) } }
+    pub fn warmup(&self) -> usize { unsafe { aeth_cc_warmup(self.h) } }
+    pub fn traceback(&self) -> usize { unsafe { aeth_cc_traceback(self.h) } }
+    /// warmup + traceback: the steps of soft values a continued `decode` wants in front
+    pub fn history(&self) -> usize { unsafe { aeth_cc_history(self.h) } }
+    /// `hist_dev`: the k - 1 bits before `bits_dev[0]` (None: zeros); `coded_dev` holds nbits * n bytes
+    pub fn encode(&mut self, hist_dev: Option<*const u8>, bits_dev: *const u8, nbits: usize, coded_dev: *mut u8, ncoded: usize) {
+        check(unsafe { aeth_cc_encode(self.h, hist_dev.unwrap_or(ptr::null()), bits_dev, nbits, coded_dev, ncoded) });
+    }
+    /// `hist_dev`: the history() * n soft values before `soft_dev[0]` (None: erasures); `bits_dev` holds nsoft / n bytes
+    pub fn decode(&mut self, hist_dev: Option<*const i8>, soft_dev: *const i8, nsoft: usize, bits_dev: *mut u8, nbits: usize) {
+        check(unsafe { aeth_cc_decode(self.h, hist_dev.unwrap_or(ptr::null()), soft_dev, nsoft, bits_dev, nbits) });
+    }
+}
+impl<'c> Drop for ConvCode<'c> { fn drop(&mut self) { unsafe { aeth_cc_destroy(self.h); } } }
+
 /// The device counterpart of `pipeline::new().add_stage(..)` (src/pipeline.rs:24-41, :123-137): five fixed stages --
 /// copy-in | upload | compute | download | copy-out -- whose compute stage is one of the library's device ops (a closure
 /// cannot cross the C ABI).  `run` takes host slices and returns what `aeth_stream_host` reports.
@@ -524,6 +557,10 @@ pub mod modem {
     /// `m.demod_naive(..)`; `compat` reproduces the reference's `idx & 1u8 << 1` output (src/modulation.rs:54)
     pub fn demod_naive(ctx: &Context, sym: &DeviceVec, bits_per_symbol: i32, bits_dev: *mut u8, nbits: usize, compat: bool) {
         check(unsafe { aeth_demod_naive(ctx.h, sym.p, sym.n, bits_per_symbol, ptr::null(), bits_dev, nbits, compat as i32) });
+    }
+    /// soft decisions for `ConvCode::decode` (no body in the reference): `bits_per_symbol` i8 values per symbol
+    pub fn demod_soft(ctx: &Context, sym: &DeviceVec, bits_per_symbol: i32, scale: f32, out_dev: *mut i8, nout: usize) {
+        check(unsafe { aeth_demod_soft(ctx.h, sym.p, sym.n, bits_per_symbol, ptr::null(), scale, out_dev, nout) });
     }
     /// `noise::new(power, seed).apply(&mut signal)` -- the double scaling of the reference is kept
     pub fn awgn_apply(ctx: &Context, signal: &mut DeviceVec, power: f32, seed: u64, offset: u64) {
