@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .context import DeviceVec
+from .resamp import call_vecs
 
 
 def step_word(ratio):
@@ -72,13 +73,7 @@ class ArbResampler:
     def exec(self, x, step, phase=None, hist=None, out=None):
         """x (and the `history` samples in front of it, or zeros) -> DeviceVec of advance(step, phase, x.n)[0] samples.
         phase None: the call starts at self.phase and leaves the next call's phase there."""
-        if not isinstance(x, DeviceVec):
-            x = self.ctx.vec(x)
-        if hist is not None and not isinstance(hist, DeviceVec):
-            hist = self.ctx.vec(hist)
-        if hist is not None and hist.n != self.history:
-            raise _lib.LengthMismatch(_lib.E_LEN, f"history holds {hist.n} samples, taps per phase - 1 = {self.history}")
-        hp = hist._p() if hist is not None and hist.n else None
+        x, hist, hp = call_vecs(self, x, hist)
         start = self.phase if phase is None else int(phase)
         count, nxt = advance(step, start, x.n)
         if out is None:

@@ -6,7 +6,8 @@
 //     out[m] = sum over p = 0 .. P - 1 ascending of (h[p L + r] + mu d[p L + r]) * s[a - p],     d[j] = h[j + 1] - h[j]
 // every product and every sum rounded (EXACT flags), the sum started from the p = 0 product.  The taps lie phase-major
 // on the device as (h, d) pairs, g[r][p] = (h[p L + r], d[p L + r]), rows padded to an even number of pairs: a lane
-// reads two taps with one 16-byte load.  The routes are those of aeth_resamp.hip:
+// reads two taps with one 16-byte load.  The routes are those of aeth_resamp.hip, and what the two files share (shape
+// constants, span load, direct fetch, tile rule, the host side of create, destroy and a launch) is in aeth_polyphase.h:
 //   staged   a workgroup makes `tile` consecutive outputs; their inputs are ONE contiguous span s[a0 - (P - 1) .. a_last],
 //            loaded coalesced into LDS once (history / zeros resolved there).  A lane issues all its span loads before
 //            the first LDS write and sums kOuts outputs side by side.  A table of at most kTabSlots 16-byte slots is
@@ -16,18 +17,14 @@
 //            inputs): a lane reads its own P samples from memory; a workgroup makes kBlock outputs.
 // The word of a workgroup's first output is one 64-bit multiply of uniform values; a lane adds e * step.  Wrap-around
 // arithmetic is exact, because the true value stays below n * 2^32 <= 2^63.
-#include "aeth_internal.h"
-
-#include <new>
+#include "aeth_polyphase.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr unsigned kMaxP = 64, kMaxLog2 = 12;
-constexpr unsigned kSpan = 4096;             // samples of LDS per workgroup: 32 KiB, four workgroups in a CU's 160 KiB
-constexpr unsigned kMaxTile = 4096;          // outputs per workgroup: 16 per lane
+using namespace aeth::poly;
+
+constexpr unsigned kMaxLog2 = 12;
 constexpr unsigned kTabSlots = 512;          // 16-byte slots of tap table a staged workgroup keeps in LDS: 8 KiB, 40 KiB with the span
-constexpr int kOuts = 4;                     // outputs a lane of the staged route sums side by side
 constexpr uint64_t kMinStep = (uint64_t)1 << 20, kMaxStep = (uint64_t)1 << 44;
 
 struct ArbCall {
@@ -40,8 +37,6 @@ struct ArbCall {
     unsigned tile;             // outputs per workgroup
 };
 
-__device__ __forceinline__ float2 mulr(float w, float2 x) { return make_float2(w * x.x, w * x.y); }
-__device__ __forceinline__ float2 add2(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 // the interpolated tap: the product rounded, then the sum rounded
 __device__ __forceinline__ float tap(float h, float d, float mu) { const float md = mu * d; return h + md; }
 
@@ -114,30 +109,7 @@ template <bool NT, bool TAB> __global__ __launch_bounds__(kBlock, 4) void arb_st
     const uint64_t f0 = t0 & 0xffffffffu;
     const unsigned span = (unsigned)((f0 + (uint64_t)(nk - 1) * step) >> 32) + P;
     const ptrdiff_t first = (ptrdiff_t)a0 - (ptrdiff_t)(P - 1);
-    if (first >= 0) {
-        // the whole span lies in the input: all of a lane's loads (kSpan / kBlock at most) are issued before the first is used
-        const float2 *src = a.in + first;
-        float2 v[kSpan / kBlock];
-#pragma unroll
-        for (unsigned j = 0; j < kSpan / kBlock; j++) {
-            const unsigned i = threadIdx.x + j * kBlock;
-            if (i < span) v[j] = aeth::nt_load<NT>(src + i);
-        }
-#pragma unroll
-        for (unsigned j = 0; j < kSpan / kBlock; j++) {
-            const unsigned i = threadIdx.x + j * kBlock;
-            if (i < span) lds[i] = v[j];
-        }
-    } else {
-        // the stream's first tiles: the span reaches into the history
-        for (unsigned i = threadIdx.x; i < span; i += kBlock) {
-            const ptrdiff_t idx = first + (ptrdiff_t)i;
-            float2 v = make_float2(0.f, 0.f);                // a history of zeros is multiplied like any other sample
-            if (idx >= 0) v = aeth::nt_load<NT>(a.in + idx);
-            else if (a.hist) v = a.hist[idx + (ptrdiff_t)(P - 1)];
-            lds[i] = v;
-        }
-    }
+    load_span<NT>(lds, a.in, a.hist, first, span, P);
     __syncthreads();
     for (unsigned e = threadIdx.x; e < nk; e += kOuts * kBlock) {
         const float4 *row[kOuts];                            // the row's first slot, in memory or in LDS
@@ -146,8 +118,7 @@ template <bool NT, bool TAB> __global__ __launch_bounds__(kBlock, 4) void arb_st
         float mu[kOuts];
 #pragma unroll
         for (int j = 0; j < kOuts; j++) {
-            const unsigned ej = e + j * kBlock < nk ? e + j * kBlock : nk - 1;    // past the tile: an output that exists, never stored
-            const uint64_t t = f0 + (uint64_t)ej * step;
+            const uint64_t t = f0 + (uint64_t)out_of(e, j, nk) * step;
             unsigned r;
             row_of(a, (unsigned)t, &r, &mu[j]);
             row[j] = (TAB ? tab : reinterpret_cast<const float4 *>(a.g)) + (size_t)r * slots;
@@ -161,7 +132,7 @@ template <bool NT, bool TAB> __global__ __launch_bounds__(kBlock, 4) void arb_st
                 if (at >= slots) at -= slots;
                 return row[j][at];
             } else return row[j][q];
-        }, [&top](int j, unsigned p) { return top[j][-(int)p]; }, acc);
+        }, SpanTaps{top}, acc);
 #pragma unroll
         for (int j = 0; j < kOuts; j++)
             if (e + j * kBlock < nk) aeth::nt_store<NT>(a.out + k0 + e + j * kBlock, acc[j]);
@@ -177,38 +148,25 @@ template <bool NT> __global__ __launch_bounds__(kBlock, 4) void arb_direct_kerne
     const uint64_t t0 = a.phase + (uint64_t)k0 * a.step;     // uniform
     const uint64_t t = t0 + (uint64_t)threadIdx.x * a.step;
     const ptrdiff_t top = (ptrdiff_t)(t >> 32);              // <= n - 1
-    const float2 *in = a.in, *hist = a.hist;
     unsigned r;
     float mu[1];
     row_of(a, (unsigned)t, &r, &mu[0]);
     const float4 *row = reinterpret_cast<const float4 *>(a.g) + (size_t)r * (a.Pp >> 1);
     float2 acc[1];
-    dot_taps<1>(P, mu, [=](int, unsigned q) { return row[q]; }, [=](int, unsigned p) {
-        const ptrdiff_t idx = top - (ptrdiff_t)p;
-        if (idx >= 0) return aeth::nt_load<NT>(in + idx);
-        return hist ? hist[idx + (ptrdiff_t)(P - 1)] : make_float2(0.f, 0.f);
-    }, acc);
+    dot_taps<1>(P, mu, [=](int, unsigned q) { return row[q]; }, Fetch<NT>{a.in, a.hist, top, P}, acc);
     aeth::nt_store<NT>(a.out + k0 + threadIdx.x, acc[0]);
 }
 
 bool step_ok(uint64_t step) { return step >= kMinStep && step <= kMaxStep; }
 
-// The largest tile (a multiple of kBlock, at most kMaxTile) whose span fits kSpan whatever the fraction of t(k0) is:
-// floor((2^32 - 1 + (tile - 1) step) / 2^32) + P <= kSpan, that is (tile - 1) step <= (kSpan - P) 2^32.
-// 0: not even kBlock outputs fit, the direct route.
-size_t tile_of(uint64_t step, size_t P)
-{
-    uint64_t tile = (((uint64_t)(kSpan - P)) << 32) / step + 1;
-    if (tile > kMaxTile) tile = kMaxTile;
-    return (size_t)(tile / kBlock * kBlock);
-}
+// tile_for: the span fits kSpan whatever the fraction of t(k0) is, floor((2^32 - 1 + (tile - 1) step) / 2^32) + P <= kSpan,
+// when (tile - 1) step <= (kSpan - P) 2^32
+size_t tile_of(uint64_t step, size_t P) { return tile_for((uint64_t)(kSpan - P) << 32, step); }
 
 }  // namespace
 
-struct aeth_arb {
-    aeth_ctx *ctx = nullptr;
-    size_t L = 0, b = 0, T = 0, P = 0, Pp = 0;
-    float2 *taps = nullptr;      // phase-major, L rows of Pp (h, d) pairs
+struct aeth_arb : aeth::poly::Resampler {        // taps: L rows of Pp (h, d) pairs
+    size_t L = 0, b = 0;
 };
 
 namespace {
@@ -272,30 +230,10 @@ int aeth_arb_create(aeth_ctx *ctx, const float *taps_host, size_t ntaps, size_t 
             const float d = hn - h;
             g[q * r->Pp + p] = make_float2(h, d);
         }
-    aeth::DeviceGuard dg(ctx->device);
-    hipStream_t st = aeth::ctx_stream(ctx);
-    hipError_t e = hipMalloc((void **)&r->taps, nt * sizeof(float2));
-    if (e == hipSuccess) e = hipMemcpyAsync(r->taps, g, nt * sizeof(float2), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    delete[] g;
-    if (e != hipSuccess) {
-        if (r->taps) (void)hipFree(r->taps);
-        delete r;
-        return aeth::hip_fail(e, "aeth_arb_create: tap upload");
-    }
-    *out = r;
-    return AETH_OK;
+    return create_finish(r, g, nt, "aeth_arb_create: tap upload", out);
 }
 
-int aeth_arb_destroy(aeth_arb *r)
-{
-    if (!r) return AETH_OK;
-    aeth::DeviceGuard dg(r->ctx->device);
-    (void)hipStreamSynchronize(aeth::ctx_stream(r->ctx));
-    if (r->taps) (void)hipFree(r->taps);
-    delete r;
-    return AETH_OK;
-}
+int aeth_arb_destroy(aeth_arb *r) { return destroy(r); }
 
 size_t aeth_arb_phases(const aeth_arb *r) { return r ? r->L : 0; }
 size_t aeth_arb_ntaps(const aeth_arb *r) { return r ? r->T : 0; }
@@ -318,39 +256,21 @@ int aeth_arb_exec(aeth_arb *r, const aeth_cf32 *hist, const aeth_cf32 *in, size_
 {
     AETH_REQUIRE(r, AETH_E_ARG, "arb is null");
     AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
-    if (r->P == 1) hist = nullptr;
     size_t want = 0;
     uint64_t next = 0;
     const int rc = aeth_arb_advance(step, phase, n, &want, &next);
     if (rc != AETH_OK) return rc;
     AETH_REQUIRE(n_out == want, AETH_E_LEN, "output holds %zu elements, %zu input samples at step %llu from phase %llu give %zu",
                  n_out, n, (unsigned long long)step, (unsigned long long)phase, want);
-    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(hist), AETH_E_ALIGN, "input or history pointer not 8-byte aligned");
-    AETH_REQUIRE(aeth::aligned8(out), AETH_E_ALIGN, "output pointer not 8-byte aligned");
-    AETH_REQUIRE(!aeth::ranges_touch(out, n_out * sizeof(aeth_cf32), in, n * sizeof(aeth_cf32)) &&
-                 !aeth::ranges_touch(out, n_out * sizeof(aeth_cf32), hist, (r->P - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
-                 "the output range overlaps the input (or its history)");
     size_t tile = tile_of(step, r->P);
     const bool staged = tile != 0;
     if (!staged) tile = kBlock;
-    const size_t grid = (n_out + tile - 1) / tile;
-    AETH_REQUIRE(grid < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu outputs in one call: more than 2^31 workgroups", n_out);
-    if (!n_out) return AETH_OK;                              // a short chunk under strong decimation makes nothing
 
     ArbCall a{};
-    a.in = (const float2 *)in;
-    a.hist = (const float2 *)hist;
-    a.out = (float2 *)out;
-    a.g = r->taps;
-    a.n_out = n_out;
+    a.g = (const float2 *)r->taps;
     a.step = step; a.phase = phase;
-    a.P = (unsigned)r->P; a.Pp = (unsigned)r->Pp; a.b = (unsigned)r->b;
-    a.tile = (unsigned)tile;
-    const bool nt = aeth::streams_past_cache((n + n_out) * sizeof(float2));
-    aeth::DeviceGuard dg(r->ctx->device);
-    hipLaunchKernelGGL(kernel_of(staged, table_fits_lds(*r), nt), dim3((unsigned)grid), dim3(kBlock), 0, aeth::ctx_stream(r->ctx), a);
-    AETH_HIP(hipGetLastError());
-    return AETH_OK;
+    a.b = (unsigned)r->b;
+    return launch(*r, hist, in, n, out, n_out, tile, a, [=](bool nt) { return kernel_of(staged, table_fits_lds(*r), nt); });
 }
 
 }  // extern "C"

@@ -126,31 +126,10 @@ template <class T> int create_planned(aeth_ctx *ctx, size_t ntaps, size_t channe
 // the object is destroyed.  `what` names the upload in a HIP error's text.
 template <class T> int create_finish(T *b, const float *taps_host, size_t scratch_elems, const char *what, T **out)
 {
-    DeviceGuard dg(b->ctx->device);
-    hipError_t e = hipMalloc((void **)&b->taps, b->L * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(b->taps, taps_host, b->L * sizeof(float), hipMemcpyHostToDevice, ctx_stream(b->ctx));
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx_stream(b->ctx));
-    if (e != hipSuccess) { (void)destroy(b); return hip_fail(e, what); }
-    if (scratch_elems) {
-        const int rc = ensure_elems(*b, scratch_elems);
-        if (rc) { (void)destroy(b); return rc; }
-    }
+    int rc = upload_table(b->ctx, taps_host, b->L * sizeof(float), &b->taps, what);
+    if (!rc && scratch_elems) rc = ensure_elems(*b, scratch_elems);
+    if (rc) { (void)destroy(b); return rc; }
     *out = b;
-    return AETH_OK;
-}
-
-// ---- what every call checks behind its lengths and before any device work: n input samples, hist_elems samples of
-// history (hist may be null), n_out output elements of out_elem_bytes each, F frames on at most `grid` workgroups ---------
-inline int check_buffers(const aeth_cf32 *hist, size_t hist_elems, const aeth_cf32 *in, size_t n, const void *out, size_t n_out,
-                         size_t out_elem_bytes, size_t grid, size_t F)
-{
-    AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(aligned8(in) && aligned8(hist), AETH_E_ALIGN, "input or history pointer not 8-byte aligned");
-    AETH_REQUIRE(((uintptr_t)out & (out_elem_bytes - 1)) == 0, AETH_E_ALIGN, "output pointer not %zu-byte aligned", out_elem_bytes);
-    AETH_REQUIRE(!ranges_touch(out, n_out * out_elem_bytes, in, n * sizeof(aeth_cf32)) &&
-                 !ranges_touch(out, n_out * out_elem_bytes, hist, hist_elems * sizeof(aeth_cf32)), AETH_E_ARG,
-                 "the output range overlaps the input (or its history)");
-    AETH_REQUIRE(grid < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu frames in one call: more than 2^31 workgroups", F);
     return AETH_OK;
 }
 

@@ -163,7 +163,7 @@ int check_call(const aeth_chan *c, const aeth_cf32 *hist, const aeth_cf32 *in, s
     AETH_REQUIRE(frames_fit(*c, F) && n_out == F * c->M, AETH_E_LEN, "output holds %zu elements, %zu frames x %zu channels give %zu",
                  n_out, F, c->M, frames_fit(*c, F) ? F * c->M : (size_t)0);
     *nframes = F;
-    return check_buffers(hist, c->L - c->D, in, n, out, n_out, out_elem_bytes, grid_bound(chan_ring(*c), c->M, ntiles_of(*c, F)), F);
+    return aeth::check_buffers(hist, c->L - c->D, in, n, out, n_out, out_elem_bytes, grid_bound(chan_ring(*c), c->M, ntiles_of(*c, F)), F, "frames");
 }
 
 }  // namespace

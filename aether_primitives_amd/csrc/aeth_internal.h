@@ -229,6 +229,30 @@ inline int check_sign_scale(int sign, int kind)
     AETH_REQUIRE(kind >= AETH_SCALE_NONE && kind <= AETH_SCALE_X, AETH_E_ARG, "bad scale kind %d", kind);
     return AETH_OK;
 }
+
+// a table built on the host goes to a new device buffer *dev on the context's stream, which is waited for; on a failure
+// nothing stays allocated, *dev is null and `what` names the upload in the HIP error's text
+int upload_table(aeth_ctx *ctx, const void *host, size_t bytes, void **dev, const char *what);
+template <class T> int upload_table(aeth_ctx *ctx, const void *host, size_t bytes, T **dev, const char *what)
+{
+    return upload_table(ctx, host, bytes, (void **)dev, what);
+}
+
+// What a call over complex samples checks behind its lengths and before any device work: n input samples, hist_elems
+// samples of history (hist may be null), n_out output elements of out_elem_bytes each, `count` of the caller's `noun`
+// ("frames", "outputs") on at most `grid` workgroups.
+inline int check_buffers(const aeth_cf32 *hist, size_t hist_elems, const aeth_cf32 *in, size_t n, const void *out, size_t n_out,
+                         size_t out_elem_bytes, size_t grid, size_t count, const char *noun)
+{
+    AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
+    AETH_REQUIRE(aligned8(in) && aligned8(hist), AETH_E_ALIGN, "input or history pointer not 8-byte aligned");
+    AETH_REQUIRE(((uintptr_t)out & (out_elem_bytes - 1)) == 0, AETH_E_ALIGN, "output pointer not %zu-byte aligned", out_elem_bytes);
+    AETH_REQUIRE(!ranges_touch(out, n_out * out_elem_bytes, in, n * sizeof(aeth_cf32)) &&
+                 !ranges_touch(out, n_out * out_elem_bytes, hist, hist_elems * sizeof(aeth_cf32)), AETH_E_ARG,
+                 "the output range overlaps the input (or its history)");
+    AETH_REQUIRE(grid < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu %s in one call: more than 2^31 workgroups", count, noun);
+    return AETH_OK;
+}
 }  // namespace aeth
 
 // message texts of the reference's panics (kept verbatim for the binding)

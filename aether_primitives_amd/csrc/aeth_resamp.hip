@@ -11,18 +11,17 @@
 //   direct   the staged tile would fall below one output per lane (Q / U above about 16): a lane reads its own P
 //            samples from memory; a workgroup makes kBlock outputs.
 // U == 1: the one tap row is the same for every lane (template flag: scalar loads).
-#include "aeth_internal.h"
+// What this file shares with aeth_arb.hip is in aeth_polyphase.h: the shape constants, the span load, the direct route's
+// sample fetch, the tile rule and the host side of create, destroy and a launch.  Here: the kernels, the tap sum, the lengths.
+#include "aeth_polyphase.h"
 
 #include <cmath>
-#include <new>
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr unsigned kMaxP = 64, kMaxRatio = 4096;
-constexpr unsigned kSpan = 4096;             // samples of LDS per workgroup: 32 KiB, four workgroups in a CU's 160 KiB
-constexpr unsigned kMaxTile = 4096;          // outputs per workgroup: 16 per lane
-constexpr int kOuts = 4;                     // outputs a lane of the staged route sums side by side
+using namespace aeth::poly;
+
+constexpr unsigned kMaxRatio = 4096;
 
 struct ResampCall {
     const float2 *in, *hist;   // hist: P - 1 samples in front of in[0], or null (zeros)
@@ -33,9 +32,6 @@ struct ResampCall {
     unsigned tile;             // outputs per workgroup
     aeth::FastDiv fd_U;
 };
-
-__device__ __forceinline__ float2 mulr(float w, float2 x) { return make_float2(w * x.x, w * x.y); }
-__device__ __forceinline__ float2 add2(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 
 // N outputs at once: acc[j] = sum over p ascending of row[j][p] * s(j, p).  The N sums are independent, so N LDS (or
 // memory) reads are in flight where one output alone would wait for each of its own.
@@ -96,44 +92,20 @@ template <bool U1, bool NT> __global__ __launch_bounds__(kBlock, 4) void resamp_
     const unsigned t_last = r0 + (nk - 1) * Q;
     const unsigned span = (U1 ? t_last : aeth::fdiv(t_last, a.fd_U)) + P;
     const ptrdiff_t first = (ptrdiff_t)a0 - (ptrdiff_t)(P - 1);
-    if (first >= 0) {
-        // the whole span lies in the input: all of a lane's loads (kSpan / kBlock at most) are issued before the first is used
-        const float2 *src = a.in + first;
-        float2 v[kSpan / kBlock];
-#pragma unroll
-        for (unsigned j = 0; j < kSpan / kBlock; j++) {
-            const unsigned i = threadIdx.x + j * kBlock;
-            if (i < span) v[j] = aeth::nt_load<NT>(src + i);
-        }
-#pragma unroll
-        for (unsigned j = 0; j < kSpan / kBlock; j++) {
-            const unsigned i = threadIdx.x + j * kBlock;
-            if (i < span) lds[i] = v[j];
-        }
-    } else {
-        // the stream's first tiles: the span reaches into the history
-        for (unsigned i = threadIdx.x; i < span; i += kBlock) {
-            const ptrdiff_t idx = first + (ptrdiff_t)i;
-            float2 v = make_float2(0.f, 0.f);                // a history of zeros is multiplied like any other sample
-            if (idx >= 0) v = aeth::nt_load<NT>(a.in + idx);
-            else if (a.hist) v = a.hist[idx + (ptrdiff_t)(P - 1)];
-            lds[i] = v;
-        }
-    }
+    load_span<NT>(lds, a.in, a.hist, first, span, P);
     __syncthreads();
     for (unsigned e = threadIdx.x; e < nk; e += kOuts * kBlock) {
         const float *row[kOuts];
         const float2 *top[kOuts];
 #pragma unroll
         for (int j = 0; j < kOuts; j++) {
-            const unsigned ej = e + j * kBlock < nk ? e + j * kBlock : nk - 1;    // past the tile: an output that exists, never stored
-            const unsigned t = r0 + ej * Q;
+            const unsigned t = r0 + out_of(e, j, nk) * Q;
             const unsigned da = U1 ? t : aeth::fdiv(t, a.fd_U);
             row[j] = a.g + (size_t)(U1 ? 0u : t - da * U) * a.Pp;
             top[j] = lds + da + (P - 1);
         }
         float2 acc[kOuts];
-        dot_taps<kOuts>(row, P, [&top](int j, unsigned p) { return top[j][-(int)p]; }, acc);
+        dot_taps<kOuts>(row, P, SpanTaps{top}, acc);
 #pragma unroll
         for (int j = 0; j < kOuts; j++)
             if (e + j * kBlock < nk) aeth::nt_store<NT>(a.out + k0 + e + j * kBlock, acc[j]);
@@ -153,36 +125,24 @@ template <bool U1, bool NT> __global__ __launch_bounds__(kBlock, 4) void resamp_
     const unsigned da = U1 ? t : aeth::fdiv(t, a.fd_U);
     const unsigned r = U1 ? 0u : t - da * U;
     const ptrdiff_t top = (ptrdiff_t)(a0 + da);              // <= n - 1
-    const float2 *in = a.in, *hist = a.hist;
     const float *row[1] = {a.g + (size_t)r * a.Pp};
     float2 acc[1];
-    dot_taps<1>(row, P, [=](int, unsigned p) {
-        const ptrdiff_t idx = top - (ptrdiff_t)p;
-        if (idx >= 0) return aeth::nt_load<NT>(in + idx);
-        return hist ? hist[idx + (ptrdiff_t)(P - 1)] : make_float2(0.f, 0.f);
-    }, acc);
+    dot_taps<1>(row, P, Fetch<NT>{a.in, a.hist, top, P}, acc);
     aeth::nt_store<NT>(a.out + k0 + threadIdx.x, acc[0]);
 }
 
-// The largest tile (a multiple of kBlock, at most kMaxTile) whose span fits kSpan whatever r0 is:
-// floor((U - 1 + (tile - 1) Q) / U) + P <= kSpan.  0: not even kBlock outputs fit, the direct route.
-size_t tile_of(size_t U, size_t Q, size_t P)
-{
-    size_t tile = (kSpan - P) * U / Q + 1;                   // U - 1 + (tile - 1) Q < (kSpan - P + 1) U
-    if (tile > kMaxTile) tile = kMaxTile;
-    return tile / kBlock * kBlock;
-}
+// tile_for: the span fits kSpan whatever r0 is, floor((U - 1 + (tile - 1) Q) / U) + P <= kSpan, when
+// U - 1 + (tile - 1) Q < (kSpan - P + 1) U
+size_t tile_of(size_t U, size_t Q, size_t P) { return tile_for((kSpan - P) * U, Q); }
 
 enum { ROUTE_STAGED = 0, ROUTE_DIRECT = 1 };
 
 }  // namespace
 
-struct aeth_resamp {
-    aeth_ctx *ctx = nullptr;
-    size_t U = 0, Q = 0, T = 0, P = 0, Pp = 0;
+struct aeth_resamp : aeth::poly::Resampler {     // taps: U rows of Pp floats
+    size_t U = 0, Q = 0;
     size_t tile = 0;
     int kind = ROUTE_STAGED;
-    float *taps = nullptr;       // phase-major, U rows of Pp
     char route[32] = {0};
 };
 
@@ -230,30 +190,10 @@ int aeth_resamp_create(aeth_ctx *ctx, const float *taps_host, size_t ntaps, size
     if (!g) { delete r; return aeth::set_error(AETH_E_NOMEM, "out of host memory"); }
     for (size_t p = 0; p < r->P; p++)
         for (size_t q = 0; q < up; q++) g[q * r->Pp + p] = taps_host[p * up + q];
-    aeth::DeviceGuard dg(ctx->device);
-    hipStream_t st = aeth::ctx_stream(ctx);
-    hipError_t e = hipMalloc((void **)&r->taps, nt * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(r->taps, g, nt * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    delete[] g;
-    if (e != hipSuccess) {
-        if (r->taps) (void)hipFree(r->taps);
-        delete r;
-        return aeth::hip_fail(e, "aeth_resamp_create: tap upload");
-    }
-    *out = r;
-    return AETH_OK;
+    return create_finish(r, g, nt, "aeth_resamp_create: tap upload", out);
 }
 
-int aeth_resamp_destroy(aeth_resamp *r)
-{
-    if (!r) return AETH_OK;
-    aeth::DeviceGuard dg(r->ctx->device);
-    (void)hipStreamSynchronize(aeth::ctx_stream(r->ctx));
-    if (r->taps) (void)hipFree(r->taps);
-    delete r;
-    return AETH_OK;
-}
+int aeth_resamp_destroy(aeth_resamp *r) { return destroy(r); }
 
 size_t aeth_resamp_up(const aeth_resamp *r) { return r ? r->U : 0; }
 size_t aeth_resamp_down(const aeth_resamp *r) { return r ? r->Q : 0; }
@@ -270,34 +210,17 @@ int aeth_resamp_exec(aeth_resamp *r, const aeth_cf32 *hist, const aeth_cf32 *in,
 {
     AETH_REQUIRE(r, AETH_E_ARG, "resamp is null");
     AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
-    if (r->P == 1) hist = nullptr;
     AETH_REQUIRE(n > 0, AETH_E_LEN, "0 input samples: a call takes at least one period of %zu", r->Q);
     AETH_REQUIRE(n % r->Q == 0, AETH_E_LEN, "%zu input samples are not a multiple of down %zu", n, r->Q);
     AETH_REQUIRE(samples_fit(*r, n), AETH_E_UNSUPPORTED, "%zu input samples at up %zu: the element counts overflow", n, r->U);
     const size_t B = n / r->Q, want = B * r->U;
     AETH_REQUIRE(n_out == want, AETH_E_LEN, "output holds %zu elements, %zu periods x up %zu give %zu", n_out, B, r->U, want);
-    AETH_REQUIRE(aeth::aligned8(in) && aeth::aligned8(hist), AETH_E_ALIGN, "input or history pointer not 8-byte aligned");
-    AETH_REQUIRE(aeth::aligned8(out), AETH_E_ALIGN, "output pointer not 8-byte aligned");
-    AETH_REQUIRE(!aeth::ranges_touch(out, n_out * sizeof(aeth_cf32), in, n * sizeof(aeth_cf32)) &&
-                 !aeth::ranges_touch(out, n_out * sizeof(aeth_cf32), hist, (r->P - 1) * sizeof(aeth_cf32)), AETH_E_ARG,
-                 "the output range overlaps the input (or its history)");
-    const size_t grid = (n_out + r->tile - 1) / r->tile;
-    AETH_REQUIRE(grid < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu outputs in one call: more than 2^31 workgroups", n_out);
 
     ResampCall a{};
-    a.in = (const float2 *)in;
-    a.hist = (const float2 *)hist;
-    a.out = (float2 *)out;
-    a.g = r->taps;
-    a.n_out = n_out;
-    a.U = (unsigned)r->U; a.Q = (unsigned)r->Q; a.P = (unsigned)r->P; a.Pp = (unsigned)r->Pp;
-    a.tile = (unsigned)r->tile;
+    a.g = (const float *)r->taps;
+    a.U = (unsigned)r->U; a.Q = (unsigned)r->Q;
     a.fd_U = aeth::make_fastdiv(a.U);
-    const bool nt = aeth::streams_past_cache((n + n_out) * sizeof(float2));
-    aeth::DeviceGuard dg(r->ctx->device);
-    hipLaunchKernelGGL(kernel_of(r->kind, r->U == 1, nt), dim3((unsigned)grid), dim3(kBlock), 0, aeth::ctx_stream(r->ctx), a);
-    AETH_HIP(hipGetLastError());
-    return AETH_OK;
+    return launch(*r, hist, in, n, out, n_out, r->tile, a, [r](bool nt) { return kernel_of(r->kind, r->U == 1, nt); });
 }
 
 int aeth_resamp_prototype(size_t up, size_t down, size_t taps_per_phase, float *out_host)

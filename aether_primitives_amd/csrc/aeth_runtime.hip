@@ -30,6 +30,19 @@ int hip_fail(hipError_t e, const char *what)
                      (int)e, hipGetErrorString(e), what);
 }
 
+int upload_table(aeth_ctx *ctx, const void *host, size_t bytes, void **dev, const char *what)
+{
+    DeviceGuard dg(ctx->device);
+    hipStream_t st = ctx_stream(ctx);
+    hipError_t e = hipMalloc(dev, bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) return AETH_OK;
+    if (*dev) (void)hipFree(*dev);
+    *dev = nullptr;
+    return hip_fail(e, what);
+}
+
 int tuning_int(const char *name, int dflt)
 {
     static const bool enabled = [] { const char *e = getenv("AETH_TUNING"); return e && atoi(e) != 0; }();

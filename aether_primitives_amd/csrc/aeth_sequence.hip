@@ -357,17 +357,9 @@ int aeth_seq_create(aeth_ctx *ctx, const struct aeth_seq_reg *regs, size_t nregs
         for (int j = 0; j < kLevels; j++)
             for (int i = 0; i < 64; i++) t[(size_t)(1 + j) * 64 + i] = pw[kChunkLog2 + j].row[i];   // P^(kChunk * 2^j)
     }
-    aeth::DeviceGuard dg(ctx->device);
-    const size_t bytes = nregs * kRegRows * sizeof(uint64_t);
-    hipError_t e = hipMalloc((void **)&s->tab_dev, bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->tab_dev, host, bytes, hipMemcpyHostToDevice, aeth::ctx_stream(ctx));
-    if (e == hipSuccess) e = hipStreamSynchronize(aeth::ctx_stream(ctx));
+    const int rc = aeth::upload_table(ctx, host, nregs * kRegRows * sizeof(uint64_t), &s->tab_dev, "aeth_seq_create: jump table upload");
     delete[] host;
-    if (e != hipSuccess) {
-        if (s->tab_dev) (void)hipFree(s->tab_dev);
-        delete[] s->pw; delete s;
-        return aeth::hip_fail(e, "aeth_seq_create: jump table upload");
-    }
+    if (rc) { delete[] s->pw; delete s; return rc; }
     *out = s;
     return AETH_OK;
 }

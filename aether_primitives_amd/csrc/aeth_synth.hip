@@ -208,7 +208,7 @@ int check_call(const aeth_synth *s, const aeth_cf32 *hist, const aeth_cf32 *in, 
     // the fold route runs the analysis bank's kernels over the M columns, the others run along the D offsets of a hop
     const size_t grid = s->kind == ROUTE_FOLD ? grid_bound(chan_ring(*s), s->M, ntiles_of(*s, F))
                                               : grid_bound(s->kind == ROUTE_RING, s->D, ntiles_of(*s, F));
-    return check_buffers(hist, (s->K - 1) * s->M, in, n, out, n_out, sizeof(aeth_cf32), grid, F);
+    return aeth::check_buffers(hist, (s->K - 1) * s->M, in, n, out, n_out, sizeof(aeth_cf32), grid, F, "frames");
 }
 
 int launch_unfold(aeth_synth *s, const aeth_cf32 *hist, const aeth_cf32 *in, size_t F, uint64_t first_frame, float2 *out)

@@ -21,6 +21,18 @@ def prototype(up, down, taps_per_phase):
     return out[:up * taps_per_phase]
 
 
+def call_vecs(rs, x, hist):
+    """x and hist of an exec call of `rs` (a Resampler or an ArbResampler) as DeviceVecs, which the caller keeps until the
+    call is made, and the pointer of the `rs.history` samples of history: None for zeros (no history, or an empty one)"""
+    if not isinstance(x, DeviceVec):
+        x = rs.ctx.vec(x)
+    if hist is not None and not isinstance(hist, DeviceVec):
+        hist = rs.ctx.vec(hist)
+    if hist is not None and hist.n != rs.history:
+        raise _lib.LengthMismatch(_lib.E_LEN, f"history holds {hist.n} samples, taps per phase - 1 = {rs.history}")
+    return x, hist, (hist._p() if hist is not None and hist.n else None)
+
+
 class Resampler:
     """Resampler(ctx, taps, up, down): `taps` holds P * up real taps.  A call reads `history` samples in front of its
     own: the previous call's last ones, or zeros."""
@@ -66,13 +78,7 @@ class Resampler:
 
     def exec(self, x, hist=None, out=None):
         """x (and the `history` samples in front of it, or zeros) -> DeviceVec of out_count(x.n) samples"""
-        if not isinstance(x, DeviceVec):
-            x = self.ctx.vec(x)
-        if hist is not None and not isinstance(hist, DeviceVec):
-            hist = self.ctx.vec(hist)
-        if hist is not None and hist.n != self.history:
-            raise _lib.LengthMismatch(_lib.E_LEN, f"history holds {hist.n} samples, taps per phase - 1 = {self.history}")
-        hp = hist._p() if hist is not None and hist.n else None
+        x, hist, hp = call_vecs(self, x, hist)
         if out is None:
             n_out = self.out_count(x.n)
             if not n_out:
