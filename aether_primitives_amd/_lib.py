@@ -29,6 +29,12 @@ class Cf32(C.Structure):
     _fields_ = [("re", C.c_float), ("im", C.c_float)]
 
 
+class SyncRecord(C.Structure):
+    """aeth_sync_record: 48 bytes"""
+    _fields_ = [("re", C.c_double), ("im", C.c_double), ("mass", C.c_double), ("n", C.c_uint64), ("n_nonfinite", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
 # name -> (restype, argtypes); mirrors include/aether_hip.h declaration by declaration
 PROTOTYPES = {
     "aeth_last_error": (C.c_char_p, []),
@@ -212,6 +218,12 @@ PROTOTYPES = {
     "aeth_nco_phasor": (i32, [u64, vp]),
     "aeth_nco_mix": (i32, [vp, vp, u64, vp, vp, sz]),
     "aeth_nco_tone": (i32, [vp, vp, u64, f32, vp, sz]),
+    "aeth_sync_chunk": (sz, []),
+    "aeth_sync_line": (i32, [vp, i32, vp, u64, vp, sz, sz, vp, vp]),
+    "aeth_sync_lag": (i32, [vp, i32, sz, vp, vp, sz, sz, vp, vp]),
+    "aeth_sync_turns": (C.c_double, [vp]),
+    "aeth_sync_freq_step": (u64, [vp, i32, sz]),
+    "aeth_sync_timing_phase": (u64, [vp, C.c_double]),
     "aeth_cc_create": (i32, [vp, vp, sz, sz, sz, pvp]),
     "aeth_cc_destroy": (i32, [vp]),
     "aeth_cc_k": (sz, [vp]),

@@ -767,6 +767,94 @@ AETH_API int aeth_nco_mix(aeth_ctx *ctx, const aeth_nco_words *w, uint64_t n0, c
 /* No body in the reference: the tone (a chirp when rate != 0) as defined above, 8 B written per sample. */
 AETH_API int aeth_nco_tone(aeth_ctx *ctx, const aeth_nco_words *w, uint64_t n0, float amp, aeth_cf32 *out_dev, size_t n);
 
+/* ---- synchronisation estimators (no body in the reference) ---- */
+/* What tells a receiver the offsets that aeth_nco_mix and aeth_arb_exec remove: the classical feed-forward estimators,
+ * each a read-only reduction over a device-resident stream (8 B per sample), none of whose samples leaves the device.
+ *   symbol timing      the spectral line of the square law at the symbol rate (Oerder and Meyr): aeth_sync_line with
+ *                      AETH_SYNC_SQUARE and step = aeth_nco_word(-1 / sps); aeth_sync_timing_phase turns it into the
+ *                      aeth_arb_exec phase of the first symbol instant
+ *   carrier phase      the M-th power sum: aeth_sync_line with AETH_SYNC_POW<M> (and NULL words); turns / M is the phase
+ *                      of the carrier, up to the M-fold ambiguity and the constellation's own angle
+ *   carrier frequency  the delay-and-multiply sum of the M-th power: aeth_sync_lag; aeth_sync_freq_step turns it into the
+ *                      aeth_nco_words.step that removes the offset
+ *
+ * The terms are defined bit for bit.  Every f32 operation is rounded on its own (no contraction):
+ *     sq(a)    = (a.re * a.re - a.im * a.im,  (a.re * a.im) + (a.re * a.im))
+ *     pw_M(x)  = x, sq(x), sq(sq(x)), sq(sq(sq(x)))               for M = 1, 2, 4, 8
+ *     q(c)     = (double)c.re * c.re + (double)c.im * c.im         as for aeth_vec_stats
+ * and every f64 expression below multiplies values that came from f32, so each product is exact and each line is ONE
+ * rounding, the same bits with or without fma.
+ *   line term i   (c, d) = the phasor of w(n0 + i), w as defined for the oscillator above (chirp term included; NULL
+ *                 words are three zeros, whose phasor is exactly (1, +0)), widened to f64
+ *                 AETH_SYNC_SQUARE:  f = q(x_i);  t = (f * c, f * d);  weight f
+ *                 AETH_SYNC_POW<M>:  z = pw_M(x_i) widened;  t.re = z.re * c - z.im * d,  t.im = z.re * d + z.im * c;
+ *                                    weight q(z)
+ *   lag term i    a = pw_M(x_i), b = pw_M(x_{i - L}), both widened, L = lag >= 1:
+ *                 t.re = a.re * b.re + a.im * b.im,  t.im = a.im * b.re - a.re * b.im;  weight q(a)
+ *                 (t = a * conj(b)).  For i < L, x_{i - L} is hist_dev[L + (i - L)] = hist_dev[i]: the L samples in front
+ *                 of the call, the library's usual history.  With hist_dev NULL the terms i < L do not exist: they are
+ *                 neither summed nor counted in n.
+ * A record holds the sum of its terms (re, im), the sum of their weights (mass: |sum| / mass is the strength of the
+ * line, 1 for a noise-free constant-modulus signal on the line), the number of terms and the number of terms with a NaN
+ * or infinite re or im.  Those terms ARE summed: IEEE decides the sum, n_nonfinite tells why.
+ *
+ * Blocks.  The n samples of a call are cut into blocks of `block` samples (0: one block of n), the last one may be short;
+ * term i belongs to block i / block and rec_dev receives ceil(n / block) records, one per block.  Any block >= 1 is
+ * accepted; blocks shorter than aeth_sync_chunk() samples take a whole workgroup each and may be slow.
+ *
+ * The order of the additions is a function of the index inside the block and of the block's length only.  A block of
+ * `len` samples is cut into chunks of C = aeth_sync_chunk() = 4096 samples, the last one short.  Inside a chunk of `left`
+ * samples the pair (2 p, 2 p + 1) with 2 p + 1 < left belongs to lane p % 256, round p / 256; the last sample of an odd
+ * `left` belongs to lane ((left - 1) / 2) % 256.
+ *   1. a lane starts re, im and mass from -0.0 -- the identity of IEEE addition, so the record of ONE term is that term,
+ *      the sign of a zero included -- and adds the terms of its pairs in round order, first sample then second, then the
+ *      odd last sample if it owns it (ascending index); a term that does not exist is skipped;
+ *   2. the 64 lanes of a wave combine by the xor butterfly 32, 16, 8, 4, 2, 1 (a + b == b + a bit for bit), the four
+ *      waves as (w0 + w1) + (w2 + w3): the chunk's record;
+ *   3. a block of one chunk is that record.  Otherwise lane t of one workgroup adds the chunk records t, t + 256, ... in
+ *      that order, from -0.0, followed by step 2;
+ *   4. the total is step 3 over the block records (an order that depends on the block count only).
+ * A record without terms is handed out with +0.0 sums.  Consequences: a block's record has the same 48 bytes at every
+ * pointer alignment (the kernels read 16 bytes per lane at any 8-byte-aligned base: no head / body / tail split), under
+ * either cache policy (AETH_NT) and on any CU count; and a stream cut at a block boundary and continued -- n0 advanced by
+ * the cut, the last L samples passed as history -- gives the same block records bit for bit.
+ *
+ * With total_host NULL a call does not wait: it is ordered on the context's in-order stream like the element-wise
+ * calls.  With total_host set it waits once; the total travels through the context's pinned bounce buffer like the
+ * record of aeth_vec_stats.  The chunk records live in a scratch buffer of the context that aeth_ctx_trim releases.
+ * Everything is validated before any device work: NULL ctx or x_dev, or both outputs NULL, AETH_E_ARG; n == 0 AETH_E_LEN
+ * as for aeth_vec_stats; an unknown kind or power AETH_E_ARG; lag == 0 or lag > 2^20 AETH_E_ARG; pointers 8-byte aligned
+ * (AETH_E_ALIGN); 2^31 workgroups or more AETH_E_UNSUPPORTED; rec_dev overlapping x_dev or hist_dev AETH_E_ARG;
+ * n0 > UINT64_MAX - n AETH_E_UNSUPPORTED, the message naming both numbers. */
+enum { AETH_SYNC_SQUARE = 0, AETH_SYNC_POW1 = 1, AETH_SYNC_POW2 = 2, AETH_SYNC_POW4 = 4, AETH_SYNC_POW8 = 8 };
+typedef struct aeth_sync_record {
+    double   re, im;        /* the complex sum                                                                 */
+    double   mass;          /* sum of the non-negative weights: |sum| / mass is the line's strength            */
+    uint64_t n;             /* terms summed                                                                    */
+    uint64_t n_nonfinite;   /* terms with a NaN or infinite component (they ARE summed; IEEE decides the sum)  */
+    uint64_t reserved;      /* 0                                                                               */
+} aeth_sync_record;         /* 48 bytes, 8-byte aligned */
+/* No body in the reference.  Host only: C, the samples one workgroup sums. */
+AETH_API size_t aeth_sync_chunk(void);
+/* No body in the reference: the line terms as defined above; `kind` is an AETH_SYNC_* value, w may be NULL (plain
+ * sums), rec_dev (ceil(n / block) records on the device) or total_host may be NULL, not both. */
+AETH_API int aeth_sync_line(aeth_ctx *ctx, int kind, const aeth_nco_words *w, uint64_t n0, const aeth_cf32 *x_dev, size_t n,
+                            size_t block, aeth_sync_record *rec_dev, aeth_sync_record *total_host);
+/* No body in the reference: the lag terms as defined above; power is 1, 2, 4 or 8, hist_dev holds `lag` samples or is
+ * NULL. */
+AETH_API int aeth_sync_lag(aeth_ctx *ctx, int power, size_t lag, const aeth_cf32 *hist_dev, const aeth_cf32 *x_dev, size_t n,
+                           size_t block, aeth_sync_record *rec_dev, aeth_sync_record *total_host);
+/* No body in the reference.  Host only, no context: atan2(im, re) / (2 pi) in f64, in [-0.5, 0.5]; 0 for NULL or a
+ * (0, 0) sum. */
+AETH_API double aeth_sync_turns(const aeth_sync_record *r);
+/* No body in the reference.  Host only: aeth_nco_word(-turns / (power * lag)), the step that REMOVES the offset a lag
+ * sum of that power and lag has seen; 0 for power <= 0 or lag == 0. */
+AETH_API uint64_t aeth_sync_freq_step(const aeth_sync_record *r, int power, size_t lag);
+/* No body in the reference.  Host only: unsigned Q32.32 of frac(-turns) * sps, truncated: the aeth_arb_exec phase of the
+ * first symbol instant, for a line taken with step = aeth_nco_word(-1 / sps) from the call's first sample.  0 unless
+ * 0 < sps <= 2^31. */
+AETH_API uint64_t aeth_sync_timing_phase(const aeth_sync_record *r, double sps);
+
 /* ---- convolutional codes: encoder and soft-decision Viterbi decoder (no body in the reference) ---- */
 /* Forward error correction between the bits and the symbols: the rate 1/n codes of constraint length k = 3 .. 7 (the
  * K = 7 codes of 802.11, DVB-S, CCSDS and LTE have 64 states, one per lane of a wave).  Everything is integer and defined

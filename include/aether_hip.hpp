@@ -674,6 +674,33 @@ private:
     uint64_t position_;
 };
 
+// ---- synchronisation estimators (no body in the reference: it estimates no offset) -----------------------------------
+// line sums a non-linearity of the samples against the oscillator's phasor (AETH_SYNC_SQUARE with step =
+// aeth_nco_word(-1 / sps): symbol timing; AETH_SYNC_POW<M> without words: the M-th power carrier phase), lag sums
+// pw_M(x[i]) * conj(pw_M(x[i - lag])) (carrier frequency).  f64 sums in a fixed order: one record per `block` samples at
+// rec_dev (device memory of ceil(n / block) records, or null) and the total, for which the call waits.
+struct Sync {
+    static size_t chunk() { return aeth_sync_chunk(); }
+    static aeth_sync_record line(Context &ctx, int kind, const DeviceVec &x, const aeth_nco_words *words = nullptr,
+                                 uint64_t position = 0, size_t block = 0, aeth_sync_record *rec_dev = nullptr)
+    {
+        aeth_sync_record total;
+        check(aeth_sync_line(ctx.get(), kind, words, position, x.ptr(), x.len(), block, rec_dev, &total));
+        return total;
+    }
+    // hist: the `lag` samples in front of x (null: the terms i < lag do not exist)
+    static aeth_sync_record lag(Context &ctx, int power, size_t lag, const DeviceVec &x, const DeviceVec *hist = nullptr,
+                                size_t block = 0, aeth_sync_record *rec_dev = nullptr)
+    {
+        aeth_sync_record total;
+        check(aeth_sync_lag(ctx.get(), power, lag, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), block, rec_dev, &total));
+        return total;
+    }
+    static double turns(const aeth_sync_record &r) { return aeth_sync_turns(&r); }
+    static uint64_t freq_step(const aeth_sync_record &r, int power, size_t lag) { return aeth_sync_freq_step(&r, power, lag); }
+    static uint64_t timing_phase(const aeth_sync_record &r, double sps) { return aeth_sync_timing_phase(&r, sps); }
+};
+
 // ---- convolutional codes (no body in the reference: it has no forward error correction) ------------------------------
 // A rate 1/n code of constraint length k = 3 .. 7, polynomials in the octal convention with the current bit at the MSB
 // (K = 7: 0171, 0133).  Device pointers in and out; bits are one byte each, soft values int8_t (positive: bit 0 likelier,

@@ -42,6 +42,10 @@ pub struct aeth_seq_reg { pub delays: *const u32, pub ndelays: usize }
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
 pub struct aeth_nco_words { pub phase: u64, pub step: u64, pub rate: u64 }
+/// aeth_sync_record: one block's (or the total's) complex f64 sum, the sum of the weights and the term counts; 48 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct aeth_sync_record { pub re: f64, pub im: f64, pub mass: f64, pub n: u64, pub n_nonfinite: u64, pub reserved: u64 }
 /// aeth_cc_code: a rate 1/n convolutional code of constraint length k; polynomials in the octal convention, current bit at the MSB
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -256,6 +260,14 @@ extern "C" {
     pub fn aeth_nco_phasor(word: u64, out_host: *mut cf32) -> c_int;
     pub fn aeth_nco_mix(ctx: *mut aeth_ctx, w: *const aeth_nco_words, n0: u64, in_dev: *const cf32, out_dev: *mut cf32, n: usize) -> c_int;
     pub fn aeth_nco_tone(ctx: *mut aeth_ctx, w: *const aeth_nco_words, n0: u64, amp: c_float, out_dev: *mut cf32, n: usize) -> c_int;
+    pub fn aeth_sync_chunk() -> usize;
+    pub fn aeth_sync_line(ctx: *mut aeth_ctx, kind: c_int, w: *const aeth_nco_words, n0: u64, x_dev: *const cf32, n: usize, block: usize,
+                          rec_dev: *mut aeth_sync_record, total_host: *mut aeth_sync_record) -> c_int;
+    pub fn aeth_sync_lag(ctx: *mut aeth_ctx, power: c_int, lag: usize, hist_dev: *const cf32, x_dev: *const cf32, n: usize, block: usize,
+                         rec_dev: *mut aeth_sync_record, total_host: *mut aeth_sync_record) -> c_int;
+    pub fn aeth_sync_turns(r: *const aeth_sync_record) -> f64;
+    pub fn aeth_sync_freq_step(r: *const aeth_sync_record, power: c_int, lag: usize) -> u64;
+    pub fn aeth_sync_timing_phase(r: *const aeth_sync_record, sps: f64) -> u64;
     pub fn aeth_cc_create(ctx: *mut aeth_ctx, code: *const aeth_cc_code, block: usize, warmup: usize, traceback: usize,
                           out: *mut *mut aeth_cc) -> c_int;
     pub fn aeth_cc_destroy(cc: *mut aeth_cc) -> c_int;

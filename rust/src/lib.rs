@@ -434,6 +434,38 @@ impl<'c> Nco<'c> {
     }
 }
 
+/// Synchronisation estimators (no body in the reference: it estimates no offset).  `line` sums a non-linearity of the
+/// samples against the oscillator's phasor (kind 0, the square law, with step = word(-1 / sps): symbol timing; kind M in
+/// 1, 2, 4, 8 without words: the M-th power carrier phase), `lag` sums pw_M(x[i]) * conj(pw_M(x[i - lag])) (carrier
+/// frequency).  f64 sums in a fixed order: one record per `block` samples at `rec_dev` (device memory of
+/// ceil(n / block) records, or None) and the total, for which the call waits.
+pub struct Sync;
+impl Sync {
+    pub const SQUARE: i32 = 0;
+    pub fn chunk() -> usize { unsafe { aeth_sync_chunk() } }
+    pub fn line(ctx: &Context, kind: i32, words: Option<&aeth_nco_words>, position: u64, x: &DeviceVec, block: usize,
+                rec_dev: Option<*mut aeth_sync_record>) -> aeth_sync_record {
+        let mut total = aeth_sync_record::default();
+        check(unsafe { aeth_sync_line(ctx.h, kind, words.map_or(ptr::null(), |w| w as *const aeth_nco_words), position, x.p, x.n, block,
+                                      rec_dev.unwrap_or(ptr::null_mut()), &mut total) });
+        total
+    }
+    /// `hist`: the `lag` samples in front of `x` (None: the terms i < lag do not exist)
+    pub fn lag(ctx: &Context, power: i32, lag: usize, hist: Option<&DeviceVec>, x: &DeviceVec, block: usize,
+               rec_dev: Option<*mut aeth_sync_record>) -> aeth_sync_record {
+        let mut total = aeth_sync_record::default();
+        check(unsafe { aeth_sync_lag(ctx.h, power, lag, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n, block,
+                                     rec_dev.unwrap_or(ptr::null_mut()), &mut total) });
+        total
+    }
+    /// atan2(im, re) / (2 pi)
+    pub fn turns(r: &aeth_sync_record) -> f64 { unsafe { aeth_sync_turns(r) } }
+    /// the oscillator step that removes the offset a lag sum of that power and lag has seen
+    pub fn freq_step(r: &aeth_sync_record, power: i32, lag: usize) -> u64 { unsafe { aeth_sync_freq_step(r, power, lag) } }
+    /// the Q32.32 phase of the first symbol instant, for a square-law line taken with step = word(-1 / sps)
+    pub fn timing_phase(r: &aeth_sync_record, sps: f64) -> u64 { unsafe { aeth_sync_timing_phase(r, sps) } }
+}
+
 /// Convolutional code (no body in the reference: it has no forward error correction): a rate 1/n code of constraint
 /// length k = 3 .. 7, polynomials in the octal convention with the current bit at the MSB (K = 7: 0o171, 0o133).  Bits are
 /// one byte each; soft values are i8, positive meaning bit 0 is likelier, 0 an erasure.  `decode` is a causal system with
