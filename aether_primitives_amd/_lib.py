@@ -224,6 +224,17 @@ PROTOTYPES = {
     "aeth_sync_turns": (C.c_double, [vp]),
     "aeth_sync_freq_step": (u64, [vp, i32, sz]),
     "aeth_sync_timing_phase": (u64, [vp, C.c_double]),
+    "aeth_ofdm_create": (i32, [vp, sz, sz, vp, sz, sz, i32, pvp]),
+    "aeth_ofdm_destroy": (i32, [vp]),
+    "aeth_ofdm_len": (sz, [vp]),
+    "aeth_ofdm_cp": (sz, [vp]),
+    "aeth_ofdm_symbol": (sz, [vp]),
+    "aeth_ofdm_carriers": (sz, [vp]),
+    "aeth_ofdm_route": (C.c_char_p, [vp]),
+    "aeth_ofdm_span": (sz, [vp, sz]),
+    "aeth_ofdm_demod": (i32, [vp, vp, sz, sz, vp, i32, f32, vp, sz]),
+    "aeth_ofdm_mod": (i32, [vp, vp, sz, sz, i32, f32, vp, sz]),
+    "aeth_ofdm_estimate": (i32, [vp, vp, vp, sz, sz, f32, i32, vp, vp, vp]),
     "aeth_cc_create": (i32, [vp, vp, sz, sz, sz, pvp]),
     "aeth_cc_destroy": (i32, [vp]),
     "aeth_cc_k": (sz, [vp]),

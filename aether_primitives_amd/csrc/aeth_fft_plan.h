@@ -46,6 +46,19 @@ struct aeth_corr {
     aeth_fir *fir = nullptr;
 };
 
+// OFDM symbols (aeth_ofdm.hip).  The plain fields come first: tests/test_ofdm_args.py hands the calls an object made by hand.
+struct aeth_ofdm {
+    aeth_ctx *ctx = nullptr;
+    size_t n_fft = 0, cp = 0, n_bins = 0, max_symbols = 0;
+    int flags = 0;
+    int fused = 0;                // the one-kernel route (power-of-two lengths 64 .. 4096 without AETH_OFDM_GENERAL)
+    aeth_fft *fft = nullptr;      // the inner plan: the fused route borrows its per-lane twiddle table, the general one runs it
+    uint32_t *bins_dev = nullptr; // bins_dev[k]: the bin of carrier k
+    int *slot_dev = nullptr;      // slot_dev[bin]: the carrier of a bin, -1 for none
+    aeth::DevScratch scratch;     // general route: n_sym contiguous frames
+    std::string route;
+};
+
 namespace aeth {
 
 enum { FFT_SPLIT_SMALL = 1, FFT_SPLIT_FAST = 2, FFT_SPLIT_FALLBACK = 3 };

@@ -55,6 +55,7 @@ typedef struct aeth_synth aeth_synth;   /* polyphase synthesis filter bank: weig
 typedef struct aeth_resamp aeth_resamp; /* polyphase rational resampler: up U, real FIR, down Q in one pass */
 typedef struct aeth_arb aeth_arb;       /* arbitrary-ratio resampler: interpolated polyphase taps behind a Q32.32 time word */
 typedef struct aeth_cc aeth_cc;         /* convolutional code: encoder and block-wise soft-decision Viterbi decoder */
+typedef struct aeth_ofdm aeth_ofdm;     /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -904,6 +905,69 @@ AETH_API int aeth_cc_encode(aeth_cc *cc, const uint8_t *hist_bits_dev, const uin
                             size_t ncoded);
 AETH_API int aeth_cc_decode(aeth_cc *cc, const int8_t *hist_soft_dev, const int8_t *soft_dev, size_t nsoft, uint8_t *bits_dev,
                             size_t nbits);
+
+/* ---- OFDM symbols (no body in the reference: it has Fft, VecOps::vec_mul and chunks_mut(fft_len) framing only) ---- */
+/* The framing and the one-tap equaliser of an OFDM link; everything else such a link needs is above (aeth_seq_scramble,
+ * aeth_cc_*, aeth_modulate, aeth_demod_soft, aeth_corr_search on a preamble, aeth_sync_lag at lag = n_fft with
+ * aeth_sync_freq_step(r, 1, n_fft) for the fractional carrier offset, aeth_nco_mix to remove it).
+ *
+ * An object is a transform length N = n_fft, a cyclic prefix of G = cp samples (0 <= G <= N), so a symbol of L = N + G
+ * samples, and a carrier list: bins[k] is the FFT bin of carrier k, in the caller's output order; K = n_bins entries,
+ * distinct and below N.
+ *
+ * Demod.  Symbol s is the window in[s L + e], e < N; the caller points in_dev at the first window sample (a timing
+ * advance into the prefix is pointer arithmetic, and the phase ramp it leaves is part of the channel the estimator sees).
+ * n_in >= aeth_ofdm_span(n_sym) = (n_sym - 1) L + N samples are read.  Y[s] is the transform of the window with the sign
+ * of Fft::fwd (AETH_SIGN_REF_FWD) and the Scale of the call, exactly the bins aeth_fft_exec gives for the same N samples.
+ *     out[s K + k] = Y[s][bins[k]]                                                 eq_dev NULL
+ *     out[s K + k] = (Y.re W.re - Y.im W.im,  Y.re W.im + Y.im W.re),  W = eq[k]   otherwise
+ * every f32 operation rounded on its own: the product aeth_vec_mul_frames makes.
+ *
+ * Mod.  Each symbol's grid is zero except grid[bins[k]] = car[s K + k]; it is transformed with the sign of Fft::bwd and the
+ * Scale of the call; time sample e goes to out[s L + G + e] and the last G of them also to out[s L + e - (N - G)].
+ * n_car = n_sym K, n_out = n_sym L.  mod followed by demod with AETH_SCALE_N on one side returns the carriers.
+ *
+ * Estimate.  y_dev holds n_sym received training symbols of K carriers (what demod wrote), x_dev the known ones: x_sym = 1
+ * (one symbol, repeated) or x_sym = n_sym.  Per carrier k, with xs = (x_sym == 1 ? 0 : s), in f64, s ascending, both sums
+ * starting from +0.0, the operands widened f32 values (so every term is ONE rounding with or without fma):
+ *     num += (yr xr + yi xi,  yi xr - yr xi)            Y[s,k] conj(X[xs,k])
+ *     den += xr xr + xi xi
+ *     H   = ((float)(num.re / den), (float)(num.im / den)), (0, 0) where den == 0
+ *     p   = hr hr + hi hi  from the rounded H widened again;   d = p + (eq_kind == AETH_OFDM_EQ_MMSE ? (double)nv : 0)
+ *     W   = ((float)(hr / d), (float)(-hi / d)), (0, 0) where d == 0;   AETH_OFDM_EQ_MATCHED: W = (hr, -hi)
+ *     csi = (float)p
+ * h_dev[k] = H, eq_dev[k] = W, csi_dev[k] = csi; any of the three may be NULL, not all.  MATCHED turns PSK carriers into
+ * CSI-weighted soft values for aeth_demod_soft with no further work.
+ *
+ * Routes.  "fused": N in {64, 128, 256, 512, 1024, 2048, 4096} -- one kernel per call, 8 (N + K) bytes per symbol (8 (L + K)
+ * for mod).  "general: <aeth_fft_route of the inner plan>": every other length aeth_fft_create accepts, and every length
+ * with AETH_OFDM_GENERAL -- windows copied to a scratch of n_sym N samples (sized at create from max_symbols; grown on
+ * demand when max_symbols is 0), the plan's transform, then the pick.  Both give the same bytes, and the bytes of
+ * aeth_fft_exec on the windows followed by aeth_vec_mul_frames.
+ *
+ * All calls are ordered on the context's stream and none waits.  Everything is validated before any device work: a NULL
+ * handle or pointer AETH_E_ARG; n_fft < 2, cp > n_fft, n_bins == 0 or > n_fft, a bin >= n_fft or listed twice, unknown flags
+ * AETH_E_ARG, the message naming the value; a length aeth_fft_create refuses: its status; n_sym above a non-zero max_symbols
+ * AETH_E_ARG; n_in < span, n_out or n_car not n_sym K resp. n_sym L AETH_E_LEN; x_sym not 1 or n_sym AETH_E_ARG; pointers
+ * 8-byte aligned (AETH_E_ALIGN; csi_dev 4); an output range that shares a byte with an input AETH_E_ARG (in place is not
+ * supported).  n_sym == 0 is an empty success for demod and mod; an estimate from no symbols is AETH_E_LEN. */
+enum { AETH_OFDM_GENERAL = 1 };          /* create flag: never take the fused route (verification, measurement) */
+enum { AETH_OFDM_EQ_ZF = 0, AETH_OFDM_EQ_MMSE = 1, AETH_OFDM_EQ_MATCHED = 2 };
+AETH_API int aeth_ofdm_create(aeth_ctx *ctx, size_t n_fft, size_t cp, const uint32_t *bins_host, size_t n_bins, size_t max_symbols,
+                              int flags, aeth_ofdm **out);
+AETH_API int aeth_ofdm_destroy(aeth_ofdm *ofdm);
+AETH_API size_t aeth_ofdm_len(const aeth_ofdm *ofdm);
+AETH_API size_t aeth_ofdm_cp(const aeth_ofdm *ofdm);
+AETH_API size_t aeth_ofdm_symbol(const aeth_ofdm *ofdm);       /* n_fft + cp */
+AETH_API size_t aeth_ofdm_carriers(const aeth_ofdm *ofdm);
+AETH_API const char *aeth_ofdm_route(const aeth_ofdm *ofdm);   /* "fused" or "general: " + the inner plan's aeth_fft_route */
+AETH_API size_t aeth_ofdm_span(const aeth_ofdm *ofdm, size_t n_sym);   /* samples demod reads; 0 for n_sym = 0 */
+AETH_API int aeth_ofdm_demod(aeth_ofdm *ofdm, const aeth_cf32 *in_dev, size_t n_in, size_t n_sym, const aeth_cf32 *eq_dev,
+                             int scale_kind, float x, aeth_cf32 *out_dev, size_t n_out);
+AETH_API int aeth_ofdm_mod(aeth_ofdm *ofdm, const aeth_cf32 *car_dev, size_t n_car, size_t n_sym, int scale_kind, float x,
+                           aeth_cf32 *out_dev, size_t n_out);
+AETH_API int aeth_ofdm_estimate(aeth_ofdm *ofdm, const aeth_cf32 *y_dev, const aeth_cf32 *x_dev, size_t n_sym, size_t x_sym, float nv,
+                                int eq_kind, aeth_cf32 *h_dev, aeth_cf32 *eq_dev, float *csi_dev);
 
 /* ---- pinned host buffers: src/pool.rs:43-221 -------------------------------------------------- */
 /* The reference's object pool ("useful for large buffers and other time expensive objects", :9-10) with pinned

@@ -740,6 +740,50 @@ private:
     aeth_cc *h_ = nullptr;
 };
 
+// ---- OFDM symbols (no body in the reference: it has Fft, vec_mul and chunks_mut(fft_len) framing only) ----------------
+// A transform length, a cyclic prefix and a carrier list (bins[k]: the FFT bin of carrier k).  demod strips the prefix,
+// transforms with the sign of Fft::fwd, picks the carriers and multiplies by eq[k] in one kernel; mod is the way back with
+// the sign of Fft::bwd; estimate sums n_sym training symbols per carrier in f64 into the channel h, the equaliser's
+// coefficients eq (AETH_OFDM_EQ_*) and csi = |h|^2.  Device pointers in and out, ordered on the context's stream.
+class Ofdm {
+public:
+    Ofdm(Context &ctx, size_t n_fft, size_t cp, const std::vector<uint32_t> &bins, size_t max_symbols = 0, bool general = false)
+    {
+        check(aeth_ofdm_create(ctx.get(), n_fft, cp, bins.data(), bins.size(), max_symbols, general ? AETH_OFDM_GENERAL : 0, &h_));
+    }
+    ~Ofdm() { aeth_ofdm_destroy(h_); }
+    Ofdm(const Ofdm &) = delete;
+    Ofdm &operator=(const Ofdm &) = delete;
+    size_t len() const { return aeth_ofdm_len(h_); }
+    size_t cp() const { return aeth_ofdm_cp(h_); }
+    size_t symbol() const { return aeth_ofdm_symbol(h_); }
+    size_t carriers() const { return aeth_ofdm_carriers(h_); }
+    std::string route() const { return aeth_ofdm_route(h_); }
+    // samples demod reads for n_sym symbols: (n_sym - 1) * symbol() + len()
+    size_t span(size_t n_sym) const { return aeth_ofdm_span(h_, n_sym); }
+    // in_dev points at the first window sample; eq_dev: carriers() coefficients or null; out_dev holds n_sym * carriers()
+    void demod(const aeth_cf32 *in_dev, size_t n_in, size_t n_sym, aeth_cf32 *out_dev, size_t n_out, const aeth_cf32 *eq_dev = nullptr,
+               Scale s = Scale::None())
+    {
+        check(aeth_ofdm_demod(h_, in_dev, n_in, n_sym, eq_dev, s.kind, s.x, out_dev, n_out));
+    }
+    // car_dev holds n_sym * carriers() carriers, out_dev n_sym * symbol() samples
+    void mod(const aeth_cf32 *car_dev, size_t n_car, size_t n_sym, aeth_cf32 *out_dev, size_t n_out, Scale s = Scale::None())
+    {
+        check(aeth_ofdm_mod(h_, car_dev, n_car, n_sym, s.kind, s.x, out_dev, n_out));
+    }
+    // x_sym: 1 (one known symbol, repeated) or n_sym; any of h_dev, eq_dev, csi_dev may be null, not all
+    void estimate(const aeth_cf32 *y_dev, const aeth_cf32 *x_dev, size_t n_sym, size_t x_sym, aeth_cf32 *h_dev, aeth_cf32 *eq_dev,
+                  float *csi_dev, int eq_kind = AETH_OFDM_EQ_ZF, float nv = 0.f)
+    {
+        check(aeth_ofdm_estimate(h_, y_dev, x_dev, n_sym, x_sym, nv, eq_kind, h_dev, eq_dev, csi_dev));
+    }
+    aeth_ofdm *get() const { return h_; }
+
+private:
+    aeth_ofdm *h_ = nullptr;
+};
+
 // ---- sequence::expand / sequence::generate for linear generators (src/sequence.rs:18-53) ----------------------------
 // A register is the set of its delays: seq[n] = XOR seq[n - d]; 1 .. 4 registers XORed (Gold codes: two).  `init` holds
 // one word per register, bit i = seq[i] (what expand() unpacks).  Device pointers in and out; bits are one byte each.

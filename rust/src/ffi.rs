@@ -13,6 +13,7 @@ use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_resamp { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_arb { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_cc { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_ofdm { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
 pub const AETH_POOL_ZERO_ON_RETURN: c_int = 1;
@@ -88,6 +89,10 @@ pub const AETH_SCALE_X: c_int = 3;
 /// and `bwd` with `FFTplanner::new(false)` (src/fft.rs:148,150).
 pub const AETH_SIGN_REF_FWD: c_int = 1;
 pub const AETH_SIGN_REF_BWD: c_int = -1;
+pub const AETH_OFDM_GENERAL: c_int = 1;
+pub const AETH_OFDM_EQ_ZF: c_int = 0;
+pub const AETH_OFDM_EQ_MMSE: c_int = 1;
+pub const AETH_OFDM_EQ_MATCHED: c_int = 2;
 
 // cf32 = Complex<f32> is repr(C) {re, im} (src/lib.rs:8-12) == aeth_cf32
 extern "C" {
@@ -268,6 +273,21 @@ extern "C" {
     pub fn aeth_sync_turns(r: *const aeth_sync_record) -> f64;
     pub fn aeth_sync_freq_step(r: *const aeth_sync_record, power: c_int, lag: usize) -> u64;
     pub fn aeth_sync_timing_phase(r: *const aeth_sync_record, sps: f64) -> u64;
+    pub fn aeth_ofdm_create(ctx: *mut aeth_ctx, n_fft: usize, cp: usize, bins_host: *const u32, n_bins: usize, max_symbols: usize,
+                            flags: c_int, out: *mut *mut aeth_ofdm) -> c_int;
+    pub fn aeth_ofdm_destroy(ofdm: *mut aeth_ofdm) -> c_int;
+    pub fn aeth_ofdm_len(ofdm: *const aeth_ofdm) -> usize;
+    pub fn aeth_ofdm_cp(ofdm: *const aeth_ofdm) -> usize;
+    pub fn aeth_ofdm_symbol(ofdm: *const aeth_ofdm) -> usize;
+    pub fn aeth_ofdm_carriers(ofdm: *const aeth_ofdm) -> usize;
+    pub fn aeth_ofdm_route(ofdm: *const aeth_ofdm) -> *const c_char;
+    pub fn aeth_ofdm_span(ofdm: *const aeth_ofdm, n_sym: usize) -> usize;
+    pub fn aeth_ofdm_demod(ofdm: *mut aeth_ofdm, in_dev: *const cf32, n_in: usize, n_sym: usize, eq_dev: *const cf32, scale_kind: c_int,
+                           x: c_float, out_dev: *mut cf32, n_out: usize) -> c_int;
+    pub fn aeth_ofdm_mod(ofdm: *mut aeth_ofdm, car_dev: *const cf32, n_car: usize, n_sym: usize, scale_kind: c_int, x: c_float,
+                         out_dev: *mut cf32, n_out: usize) -> c_int;
+    pub fn aeth_ofdm_estimate(ofdm: *mut aeth_ofdm, y_dev: *const cf32, x_dev: *const cf32, n_sym: usize, x_sym: usize, nv: c_float,
+                              eq_kind: c_int, h_dev: *mut cf32, eq_dev: *mut cf32, csi_dev: *mut c_float) -> c_int;
     pub fn aeth_cc_create(ctx: *mut aeth_ctx, code: *const aeth_cc_code, block: usize, warmup: usize, traceback: usize,
                           out: *mut *mut aeth_cc) -> c_int;
     pub fn aeth_cc_destroy(cc: *mut aeth_cc) -> c_int;

@@ -499,6 +499,46 @@ impl<'c> ConvCode<'c> {
 }
 impl<'c> Drop for ConvCode<'c> { fn drop(&mut self) { unsafe { aeth_cc_destroy(self.h); } } }
 
+/// OFDM symbols (no body in the reference: it has `Fft`, `vec_mul` and `chunks_mut(fft_len)` framing only): a transform
+/// length, a cyclic prefix and a carrier list (`bins[k]`: the FFT bin of carrier k).  `demod` strips the prefix, transforms
+/// with the sign of `Fft::fwd`, picks the carriers and multiplies by `eq[k]` in one kernel; `modulate` is the way back with
+/// the sign of `Fft::bwd`; `estimate` sums the training symbols per carrier in f64.
+pub struct Ofdm<'c> { h: *mut aeth_ofdm, _ctx: &'c Context }
+impl<'c> Ofdm<'c> {
+    /// `max_symbols`: the symbols of one call at most (0: no bound); `general`: never take the fused kernel
+    pub fn new(ctx: &'c Context, n_fft: usize, cp: usize, bins: &[u32], max_symbols: usize, general: bool) -> Ofdm<'c> {
+        let mut h = ptr::null_mut();
+        check(unsafe { aeth_ofdm_create(ctx.h, n_fft, cp, bins.as_ptr(), bins.len(), max_symbols, if general { AETH_OFDM_GENERAL } else { 0 }, &mut h) });
+        Ofdm { h, _ctx: ctx }
+    }
+    pub fn len(&self) -> usize { unsafe { aeth_ofdm_len(self.h) } }
+    pub fn cp(&self) -> usize { unsafe { aeth_ofdm_cp(self.h) } }
+    pub fn symbol(&self) -> usize { unsafe { aeth_ofdm_symbol(self.h) } }
+    pub fn carriers(&self) -> usize { unsafe { aeth_ofdm_carriers(self.h) } }
+    pub fn route(&self) -> String { unsafe { std::ffi::CStr::from_ptr(aeth_ofdm_route(self.h)) }.to_string_lossy().into_owned() }
+    /// samples `demod` reads for `n_sym` symbols: (n_sym - 1) * symbol() + len()
+    pub fn span(&self, n_sym: usize) -> usize { unsafe { aeth_ofdm_span(self.h, n_sym) } }
+    /// `x` starts at the first window sample; `eq`: carriers() coefficients; `out` holds n_sym * carriers()
+    pub fn demod(&mut self, x: &DeviceVec, n_sym: usize, eq: Option<&DeviceVec>, scale: Scale, out: &mut DeviceVec) {
+        let (k, s) = scale_args(scale);
+        check(unsafe { aeth_ofdm_demod(self.h, x.p, x.n, n_sym, eq.map_or(ptr::null(), |e| e.p as *const cf32), k, s, out.p, out.n) });
+    }
+    /// `carriers` holds n_sym * carriers(), `out` n_sym * symbol() samples
+    pub fn modulate(&mut self, carriers: &DeviceVec, n_sym: usize, scale: Scale, out: &mut DeviceVec) {
+        let (k, s) = scale_args(scale);
+        check(unsafe { aeth_ofdm_mod(self.h, carriers.p, carriers.n, n_sym, k, s, out.p, out.n) });
+    }
+    /// `y`: n_sym received training symbols, `x_known`: one symbol or n_sym of them; `eq_kind`: AETH_OFDM_EQ_*; any output may be
+    /// None, not all
+    pub fn estimate(&mut self, y: &DeviceVec, x_known: &DeviceVec, n_sym: usize, nv: f32, eq_kind: i32, h: Option<&mut DeviceVec>,
+                    eq: Option<&mut DeviceVec>, csi: Option<&mut DeviceF32>) {
+        let x_sym = if self.carriers() > 0 { x_known.n / self.carriers() } else { 0 };
+        check(unsafe { aeth_ofdm_estimate(self.h, y.p, x_known.p, n_sym, x_sym, nv, eq_kind, h.map_or(ptr::null_mut(), |v| v.p),
+                                          eq.map_or(ptr::null_mut(), |v| v.p), csi.map_or(ptr::null_mut(), |v| v.p)) });
+    }
+}
+impl<'c> Drop for Ofdm<'c> { fn drop(&mut self) { unsafe { aeth_ofdm_destroy(self.h); } } }
+
 /// The device counterpart of `pipeline::new().add_stage(..)` (src/pipeline.rs:24-41, :123-137): five fixed stages --
 /// copy-in | upload | compute | download | copy-out -- whose compute stage is one of the library's device ops (a closure
 /// cannot cross the C ABI).  `run` takes host slices and returns what `aeth_stream_host` reports.
