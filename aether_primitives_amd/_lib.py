@@ -35,6 +35,12 @@ class SyncRecord(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class MovPeak(C.Structure):
+    """aeth_mov_peak: 64 bytes"""
+    _fields_ = [("index", C.c_uint64), ("first", C.c_uint64), ("p_re", C.c_double), ("p_im", C.c_double), ("r", C.c_double),
+                ("r_lag", C.c_double), ("metric", C.c_float), ("n_nan", C.c_uint32), ("reserved", C.c_uint64)]
+
+
 # name -> (restype, argtypes); mirrors include/aether_hip.h declaration by declaration
 PROTOTYPES = {
     "aeth_last_error": (C.c_char_p, []),
@@ -224,6 +230,11 @@ PROTOTYPES = {
     "aeth_sync_turns": (C.c_double, [vp]),
     "aeth_sync_freq_step": (u64, [vp, i32, sz]),
     "aeth_sync_timing_phase": (u64, [vp, C.c_double]),
+    "aeth_mov_history": (sz, [i32, sz, sz]),
+    "aeth_mov_grid": (sz, [i32, sz]),
+    "aeth_mov_freq_step": (u64, [vp, sz]),
+    "aeth_mov_exec": (i32, [vp, i32, sz, sz, vp, vp, sz, vp, vp, vp]),
+    "aeth_mov_search": (i32, [vp, i32, sz, sz, C.c_double, C.c_double, vp, vp, sz, sz, vp, vp]),
     "aeth_ofdm_create": (i32, [vp, sz, sz, vp, sz, sz, i32, pvp]),
     "aeth_ofdm_destroy": (i32, [vp]),
     "aeth_ofdm_len": (sz, [vp]),

@@ -55,7 +55,8 @@ struct aeth_ctx {
     //   stats_slab  per-workgroup partial records of aeth_vec_stats (aeth_stats.hip)
     //   corr_slab   per-wave and per-workgroup records of aeth_corr_search (aeth_fir.hip)
     //   sync_slab   per-chunk and per-block records of aeth_sync_line / aeth_sync_lag (aeth_sync.hip)
-    aeth::DevScratch stage[2], stats_slab, corr_slab, sync_slab;
+    //   mov_slab    per-chunk and per-block records of aeth_mov_search (aeth_mov.hip)
+    aeth::DevScratch stage[2], stats_slab, corr_slab, sync_slab, mov_slab;
     // small host-slice calls: two pinned, device-visible bounce buffers (aeth::HostIO)
     void *bounce[2] = {nullptr, nullptr};
     // plans of the one-shot vec_fft / vec_ifft (aeth_fft.hip: fft_cache_get), most recently used first
@@ -94,9 +95,9 @@ int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes, bool slack = true
 // aeth_ctx_destroy does not)
 hipError_t scratch_release(DevScratch &s);
 // every scratch buffer of the context
-inline std::array<DevScratch *, 5> ctx_scratch(aeth_ctx *ctx)
+inline std::array<DevScratch *, 6> ctx_scratch(aeth_ctx *ctx)
 {
-    return {&ctx->stage[0], &ctx->stage[1], &ctx->stats_slab, &ctx->corr_slab, &ctx->sync_slab};
+    return {&ctx->stage[0], &ctx->stage[1], &ctx->stats_slab, &ctx->corr_slab, &ctx->sync_slab, &ctx->mov_slab};
 }
 // ensure staging slot `i` holds >= bytes of device memory (an unused slot still gets 16 bytes)
 inline int ctx_stage(aeth_ctx *ctx, int i, size_t bytes) { return scratch_ensure(ctx, ctx->stage[i], bytes ? bytes : 16); }

@@ -856,6 +856,99 @@ AETH_API uint64_t aeth_sync_freq_step(const aeth_sync_record *r, int power, size
  * 0 < sps <= 2^31. */
 AETH_API uint64_t aeth_sync_timing_phase(const aeth_sync_record *r, double sps);
 
+/* ---- moving-window detectors (no body in the reference) ---- */
+/* What a burst receiver starts with: a sliding window over a device-resident stream, one value per sample, no known
+ * sequence.  One kernel family serves three uses:
+ *   timing metric     delay-and-correlate over a repeated training half (Schmidl and Cox: L = W = N / 2) or over the
+ *                     cyclic prefix (L = N, W = the prefix): AETH_MOV_LAG
+ *   energy detector   squelch, burst edges, the level an AGC follows: AETH_MOV_POWER
+ *   carrier offset    the angle of the lag sum at the detected instant: aeth_mov_freq_step of a search record
+ *
+ * Terms.  Every f64 line is one rounding of products of widened f32 values, as for the estimators above:
+ *     e_j = q(x_j) = (double)re * re + (double)im * im
+ *     c_j = x_j * conj(x_{j - L}):  c.re = a.re * b.re + a.im * b.im,  c.im = a.im * b.re - a.re * b.im,  a = x_j, b = x_{j - L}
+ * (the lag term of aeth_sync_lag at power 1).  x_j for j < 0 is hist_dev[H + j], H = aeth_mov_history(kind, window, lag):
+ * W - 1 + L samples for the lag kind, W - 1 for the power kind.  A NULL hist_dev means ZEROS: the system is causal with
+ * zero initial state, like the FIR.  (This differs from aeth_sync_lag, where terms in front of the call without history
+ * do not exist.)
+ *
+ * Windows.  For every output i in [0, n), W = window:
+ *     P(i) = sum of c_j,  R(i) = sum of e_j,  j = i - W + 1 .. i
+ * The partner power of the lag kind is R(i - L): the same sum further back, not a third quantity.
+ *
+ * Metric, in f64, each multiplication, the addition and the division rounded on its own (these products are not exact:
+ * the library is built without contraction), then rounded to f32:
+ *     AETH_MOV_LAG     num = P.re * P.re + P.im * P.im;  den = R(i) * R(i - L);  M(i) = den == 0 ? +0.0f : (float)(num / den)
+ *                      (M <= 1 up to rounding by Cauchy-Schwarz; 1 where the window repeats exactly, and at W = 1 for
+ *                      any finite non-zero pair)
+ *     AETH_MOV_POWER   (lag must be 0)  M(i) = (float)(R(i) / (double)W): the moving mean power
+ *
+ * The order of the additions is a function of W and of the output's index in the call only: not of the pointer, the
+ * cache policy (AETH_NT), the CU count, `block`, or the planes requested; aeth_mov_exec and aeth_mov_search see the same
+ * f64 sums.  A window sum adds that window's own W terms and nothing else (no running sum is differenced: a window behind
+ * a strong burst does not inherit the burst's rounding error).  It is van Herk's scheme over segments [s W, (s + 1) W)
+ * counted from the call's index 0 (history lies in segments -1, -2, ...).  Term j has position k = j - s W in its segment
+ * and lies in cell c = k / 32; a segment has cps = ceil(W / 32) cells, the last one short when 32 does not divide W:
+ *     a(k) = the cell's terms from its first through k, added in ascending order from -0.0
+ *     d(k) = the cell's terms from its last down to k, added in descending order from -0.0
+ *     T_c  = a(last k of cell c)
+ *     v    = the log-step scan of T_0 .. T_{cps - 1}: for s = 1, 2, 4, ... < cps:  v[c] = v[c - s] + v[c] for all c >= s at once
+ *     u    = the same scan of the totals in reverse order, T_{cps - 1} .. T_0
+ *     h(k) = a(k) for c == 0, else v[c - 1] + a(k)                 (the segment's terms 0 .. k)
+ *     g(k) = d(k) for c == cps - 1, else u[cps - 2 - c] + d(k)     (the segment's terms k .. W - 1)
+ *     S(i) = h(W - 1) of i's segment when i mod W == W - 1, else g(k + 1) of the segment in front + h(k) of i's own, k = i mod W
+ * Sums start from -0.0 (the identity of IEEE addition), so W = 1 hands out each term itself, the sign of a zero included.
+ * tests/mov_truth.py restates this in numpy.  Cuts: aeth_mov_grid(kind, window) = W.  A stream cut at a multiple of it
+ * and continued with the last H samples as history (zeros where the stream is shorter than H) gives planes byte for byte
+ * those of one call.
+ *
+ * aeth_mov_exec writes the planes that are not NULL -- p_dev: cf32 ((float)P.re, (float)P.im), lag kind only; r_dev:
+ * (float)R(i); m_dev: M(i) -- 8 B read per sample (the partner range is a second read that the caches serve for small L),
+ * 4 or 8 B written per plane.  It is stream-ordered and does not wait.
+ *
+ * aeth_mov_search writes no plane: one 64-byte record per `block` samples (0: one block of n; the last block may be
+ * short; peaks_dev holds ceil(n / block) records; blocks shorter than 1024 samples take a workgroup each).  Output i is a
+ * CANDIDATE when M(i) is not NaN, R(i) >= r_min and, for the lag kind, R(i - L) >= r_min.  `index` is the candidate with
+ * the largest M, ties to the lowest index, counted from the call's first sample; `first` the lowest candidate with
+ * (double)M >= threshold (n when there is none); p_re, p_im, r, r_lag the f64 sums at `index` (the power kind: r only, the
+ * others +0.0); metric = M(index); n_nan the block's count of outputs whose M is NaN, saturating.  A block without a
+ * candidate reports index = first = n, metric = NaN and +0.0 sums.  best_host (may be NULL; not both outputs NULL) waits
+ * once and returns the same record over the whole call; it travels through the context's pinned bounce buffer like the
+ * total of aeth_sync_*.  Chunk records live in a scratch buffer of the context that aeth_ctx_trim releases.  No
+ * floating-point atomics anywhere.
+ *
+ * Everything is refused before any device work, the message naming the offending value: NULL ctx or x_dev, or every
+ * output NULL, AETH_E_ARG; n == 0 AETH_E_LEN; an unknown kind AETH_E_ARG; window == 0 AETH_E_ARG; window > 4096
+ * AETH_E_UNSUPPORTED; the lag kind with lag == 0 AETH_E_ARG, with lag > 65536 AETH_E_UNSUPPORTED; the power kind with
+ * lag != 0 or with p_dev AETH_E_ARG; r_min negative or NaN, threshold NaN AETH_E_ARG; x_dev, hist_dev, p_dev, peaks_dev
+ * (or best_host) not 8-byte aligned, r_dev or m_dev not 4-byte aligned AETH_E_ALIGN; any output overlapping an input or
+ * another output AETH_E_ARG; 2^31 workgroups or more AETH_E_UNSUPPORTED. */
+enum { AETH_MOV_LAG = 0, AETH_MOV_POWER = 1 };
+typedef struct aeth_mov_peak {
+    uint64_t index;         /* the candidate with the largest metric (lowest index of equals); n when there is none */
+    uint64_t first;         /* the lowest candidate with metric >= threshold; n when there is none                  */
+    double   p_re, p_im;    /* P(index)                                                                             */
+    double   r, r_lag;      /* R(index), R(index - L)                                                               */
+    float    metric;        /* M(index); NaN when there is no candidate                                             */
+    uint32_t n_nan;         /* outputs whose M is NaN (saturating)                                                  */
+    uint64_t reserved;      /* 0                                                                                    */
+} aeth_mov_peak;            /* 64 bytes, 8-byte aligned */
+/* No body in the reference.  Host only: H, the samples of history a call takes; 0 for an unknown kind or window == 0. */
+AETH_API size_t aeth_mov_history(int kind, size_t window, size_t lag);
+/* No body in the reference.  Host only: the cut granularity G = window; 0 for an unknown kind or a window the calls
+ * refuse. */
+AETH_API size_t aeth_mov_grid(int kind, size_t window);
+/* No body in the reference.  Host only: aeth_nco_word(-atan2(p_im, p_re) / (2 pi lag)), the step that REMOVES the offset
+ * the lag sum of the record has seen (aeth_sync_freq_step at power 1); 0 for NULL, a zero sum or lag == 0. */
+AETH_API uint64_t aeth_mov_freq_step(const aeth_mov_peak *p, size_t lag);
+/* No body in the reference: the planes as defined above; any of p_dev, r_dev, m_dev may be NULL, not all. */
+AETH_API int aeth_mov_exec(aeth_ctx *ctx, int kind, size_t window, size_t lag, const aeth_cf32 *hist_dev, const aeth_cf32 *x_dev,
+                           size_t n, aeth_cf32 *p_dev, float *r_dev, float *m_dev);
+/* No body in the reference: the search records as defined above; peaks_dev or best_host may be NULL, not both. */
+AETH_API int aeth_mov_search(aeth_ctx *ctx, int kind, size_t window, size_t lag, double r_min, double threshold,
+                             const aeth_cf32 *hist_dev, const aeth_cf32 *x_dev, size_t n, size_t block, aeth_mov_peak *peaks_dev,
+                             aeth_mov_peak *best_host);
+
 /* ---- convolutional codes: encoder and soft-decision Viterbi decoder (no body in the reference) ---- */
 /* Forward error correction between the bits and the symbols: the rate 1/n codes of constraint length k = 3 .. 7 (the
  * K = 7 codes of 802.11, DVB-S, CCSDS and LTE have 64 states, one per lane of a wave).  Everything is integer and defined

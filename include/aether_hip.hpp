@@ -701,6 +701,30 @@ struct Sync {
     static uint64_t timing_phase(const aeth_sync_record &r, double sps) { return aeth_sync_timing_phase(&r, sps); }
 };
 
+// ---- moving-window detectors (no body in the reference) --------------------------------------------------------------
+// For every sample the sum of the last `window` lag terms x[j] * conj(x[j - lag]) (P) and powers (R), and the metric
+// |P|^2 / (R(i) R(i - lag)) (AETH_MOV_LAG) or the moving mean power (AETH_MOV_POWER, lag 0).  exec writes the planes that
+// are not null and does not wait; search keeps one record per `block` samples at peaks_dev (or null) and returns the
+// record over the whole call, for which it waits.  hist: the history() samples in front of x (null: zeros).
+struct Mov {
+    static size_t history(int kind, size_t window, size_t lag) { return aeth_mov_history(kind, window, lag); }
+    static size_t grid(int kind, size_t window) { return aeth_mov_grid(kind, window); }
+    static void exec(Context &ctx, int kind, size_t window, size_t lag, const DeviceVec &x, aeth_cf32 *p_dev, float *r_dev, float *m_dev,
+                     const DeviceVec *hist = nullptr)
+    {
+        check(aeth_mov_exec(ctx.get(), kind, window, lag, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), p_dev, r_dev, m_dev));
+    }
+    static aeth_mov_peak search(Context &ctx, int kind, size_t window, size_t lag, double r_min, double threshold, const DeviceVec &x,
+                                const DeviceVec *hist = nullptr, size_t block = 0, aeth_mov_peak *peaks_dev = nullptr)
+    {
+        aeth_mov_peak best;
+        check(aeth_mov_search(ctx.get(), kind, window, lag, r_min, threshold, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), block,
+                              peaks_dev, &best));
+        return best;
+    }
+    static uint64_t freq_step(const aeth_mov_peak &p, size_t lag) { return aeth_mov_freq_step(&p, lag); }
+};
+
 // ---- convolutional codes (no body in the reference: it has no forward error correction) ------------------------------
 // A rate 1/n code of constraint length k = 3 .. 7, polynomials in the octal convention with the current bit at the MSB
 // (K = 7: 0171, 0133).  Device pointers in and out; bits are one byte each, soft values int8_t (positive: bit 0 likelier,

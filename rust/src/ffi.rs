@@ -47,6 +47,12 @@ pub struct aeth_nco_words { pub phase: u64, pub step: u64, pub rate: u64 }
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
 pub struct aeth_sync_record { pub re: f64, pub im: f64, pub mass: f64, pub n: u64, pub n_nonfinite: u64, pub reserved: u64 }
+/// aeth_mov_peak: the best candidate of a block of moving-window outputs (or of the call), the f64 sums there; 64 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct aeth_mov_peak { pub index: u64, pub first: u64, pub p_re: f64, pub p_im: f64, pub r: f64, pub r_lag: f64, pub metric: f32,
+                           pub n_nan: u32, pub reserved: u64 }
+pub const AETH_MOV_LAG: c_int = 0; pub const AETH_MOV_POWER: c_int = 1;
 /// aeth_cc_code: a rate 1/n convolutional code of constraint length k; polynomials in the octal convention, current bit at the MSB
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -273,6 +279,13 @@ extern "C" {
     pub fn aeth_sync_turns(r: *const aeth_sync_record) -> f64;
     pub fn aeth_sync_freq_step(r: *const aeth_sync_record, power: c_int, lag: usize) -> u64;
     pub fn aeth_sync_timing_phase(r: *const aeth_sync_record, sps: f64) -> u64;
+    pub fn aeth_mov_history(kind: c_int, window: usize, lag: usize) -> usize;
+    pub fn aeth_mov_grid(kind: c_int, window: usize) -> usize;
+    pub fn aeth_mov_freq_step(p: *const aeth_mov_peak, lag: usize) -> u64;
+    pub fn aeth_mov_exec(ctx: *mut aeth_ctx, kind: c_int, window: usize, lag: usize, hist_dev: *const cf32, x_dev: *const cf32, n: usize,
+                         p_dev: *mut cf32, r_dev: *mut f32, m_dev: *mut f32) -> c_int;
+    pub fn aeth_mov_search(ctx: *mut aeth_ctx, kind: c_int, window: usize, lag: usize, r_min: f64, threshold: f64, hist_dev: *const cf32,
+                           x_dev: *const cf32, n: usize, block: usize, peaks_dev: *mut aeth_mov_peak, best_host: *mut aeth_mov_peak) -> c_int;
     pub fn aeth_ofdm_create(ctx: *mut aeth_ctx, n_fft: usize, cp: usize, bins_host: *const u32, n_bins: usize, max_symbols: usize,
                             flags: c_int, out: *mut *mut aeth_ofdm) -> c_int;
     pub fn aeth_ofdm_destroy(ofdm: *mut aeth_ofdm) -> c_int;

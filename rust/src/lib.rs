@@ -466,6 +466,33 @@ impl Sync {
     pub fn timing_phase(r: &aeth_sync_record, sps: f64) -> u64 { unsafe { aeth_sync_timing_phase(r, sps) } }
 }
 
+/// Moving-window detectors (no body in the reference): for every sample the sum of the last `window` lag terms
+/// x[j] * conj(x[j - lag]) and powers, the timing metric |P|^2 / (R(i) R(i - lag)) (kind `AETH_MOV_LAG`) or the moving mean
+/// power (`AETH_MOV_POWER`, lag 0).  `hist`: the `history()` samples in front of `x` (None: zeros).
+pub struct Mov;
+impl Mov {
+    pub fn history(kind: i32, window: usize, lag: usize) -> usize { unsafe { aeth_mov_history(kind, window, lag) } }
+    /// a stream cut at a multiple of this continues bit for bit
+    pub fn grid(kind: i32, window: usize) -> usize { unsafe { aeth_mov_grid(kind, window) } }
+    /// the planes that are given: P as cf32, R and the metric as f32, one value per sample; stream-ordered, no wait
+    pub fn exec(ctx: &Context, kind: i32, window: usize, lag: usize, hist: Option<&DeviceVec>, x: &DeviceVec, p: Option<&mut DeviceVec>,
+                r_dev: Option<*mut f32>, m_dev: Option<*mut f32>) {
+        check(unsafe { aeth_mov_exec(ctx.h, kind, window, lag, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n,
+                                     p.map_or(ptr::null_mut(), |v| v.p), r_dev.unwrap_or(ptr::null_mut()), m_dev.unwrap_or(ptr::null_mut())) });
+    }
+    /// one record per `block` samples at `peaks_dev` (device memory of ceil(n / block) records, or None) and the record
+    /// over the whole call, for which the call waits
+    pub fn search(ctx: &Context, kind: i32, window: usize, lag: usize, r_min: f64, threshold: f64, hist: Option<&DeviceVec>, x: &DeviceVec,
+                  block: usize, peaks_dev: Option<*mut aeth_mov_peak>) -> aeth_mov_peak {
+        let mut best = aeth_mov_peak::default();
+        check(unsafe { aeth_mov_search(ctx.h, kind, window, lag, r_min, threshold, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n,
+                                       block, peaks_dev.unwrap_or(ptr::null_mut()), &mut best) });
+        best
+    }
+    /// the oscillator step that removes the offset the lag sum of the record has seen
+    pub fn freq_step(p: &aeth_mov_peak, lag: usize) -> u64 { unsafe { aeth_mov_freq_step(p, lag) } }
+}
+
 /// Convolutional code (no body in the reference: it has no forward error correction): a rate 1/n code of constraint
 /// length k = 3 .. 7, polynomials in the octal convention with the current bit at the MSB (K = 7: 0o171, 0o133).  Bits are
 /// one byte each; soft values are i8, positive meaning bit 0 is likelier, 0 an erasure.  `decode` is a causal system with
