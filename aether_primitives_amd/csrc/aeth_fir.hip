@@ -180,6 +180,7 @@ __device__ __forceinline__ void best_take(double &q, unsigned long long &idx, un
 }
 
 // the workgroup's 256 candidates -> one, valid in thread 0
+// (not aeth_reduce.h's block_reduce: held as a record, the candidate costs both corr kernels private memory)
 __device__ __forceinline__ void best_block_reduce(double &q, unsigned long long &idx, unsigned long long &nnan, double *lq,
                                                   unsigned long long *li, unsigned long long *ln)
 {

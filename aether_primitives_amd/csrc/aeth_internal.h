@@ -52,10 +52,10 @@ struct aeth_ctx {
     // Device scratch, one buffer per user -- they are held at the same time (aeth_fir_exec_host keeps both staging slots
     // across its launch; aeth_corr_search keeps its slab while HostIO may hold stage[1]):
     //   stage[2]    the host-slice flavours' input / output (ctx_stage)
-    //   stats_slab  per-workgroup partial records of aeth_vec_stats (aeth_stats.hip)
+    //   stats_slab  per-chunk records of aeth_vec_stats (aeth_stats.hip)
     //   corr_slab   per-wave and per-workgroup records of aeth_corr_search (aeth_fir.hip)
-    //   sync_slab   per-chunk and per-block records of aeth_sync_line / aeth_sync_lag (aeth_sync.hip)
-    //   mov_slab    per-chunk and per-block records of aeth_mov_search (aeth_mov.hip)
+    //   sync_slab   [chunk records][block records] of aeth_sync_line / aeth_sync_lag (aeth_sync.hip), and
+    //   mov_slab    the same of aeth_mov_search (aeth_mov.hip): the layout is aeth::red::run_blocks' (aeth_reduce.h)
     aeth::DevScratch stage[2], stats_slab, corr_slab, sync_slab, mov_slab;
     // small host-slice calls: two pinned, device-visible bounce buffers (aeth::HostIO)
     void *bounce[2] = {nullptr, nullptr};
@@ -136,6 +136,7 @@ int tuning_int(const char *name, int dflt);
 constexpr int lab_int(const char *, int dflt) { return dflt; }
 #endif
 
+inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // [a, a + na) and [b, b + nb) share a byte?  (never for a null pointer or an empty range)

@@ -28,23 +28,25 @@
 //      of 1024 slots, one slot of padding per 32: a lane's slots are 32 apart and would share one bank otherwise);
 //   3. a(k) ascending, + v: h of every output of the chunk, + the g of step 2: the window sums, the metric, and either
 //      the planes (staged in the slots just read, then stored 256 consecutive outputs at a time) or the lane's best
-//      candidate, which a butterfly over the workgroup turns into the chunk's record.
+//      candidate, which THE TREE of aeth_reduce.h turns into the chunk's record (the folds behind it: the same file).
 // Windows up to 1024 samples first copy the chunk's samples and their lag partners into LDS, 256 consecutive samples per
 // load instruction, and the passes read those; longer windows read memory in every pass, 32 consecutive samples per lane (a
 // line of the vector cache per lane): slow, and measured as such.  Samples in front of the call come
 // from the history (or are zeros) by a select on the address.
 #include "aeth_internal.h"
+#include "aeth_reduce.h"
 
 #include <cmath>
 
 namespace {
 
 using aeth::FastDiv;
+using aeth::red::Cut;
 
 typedef aeth_mov_peak Peak;
 static_assert(sizeof(Peak) == 64, "record layout");
 
-constexpr int kBlock = 256;
+constexpr int kBlock = aeth::red::kBlock;
 constexpr unsigned kChunk = 1024;                                    // outputs per workgroup
 constexpr int kCell = 32;                                            // terms a lane adds in order
 constexpr size_t kMaxWindow = 4096;
@@ -84,21 +86,6 @@ struct Args {
     Cand *rec;
     int direct;
 };
-
-// where a workgroup works: block b, chunk k of it -> first output (g), outputs (left)
-struct Geo { unsigned b; size_t g; int left; };
-__device__ __forceinline__ Geo geo_of(size_t n, size_t block, const FastDiv &cpb)
-{
-    Geo o;
-    o.b = aeth::fdiv(blockIdx.x, cpb);
-    const unsigned k = blockIdx.x - o.b * cpb.d;
-    const size_t bstart = (size_t)o.b * block;
-    const size_t blen = n - bstart < block ? n - bstart : block;
-    const size_t cstart = (size_t)k * kChunk;                        // < blen: the grid holds ceil(blen / kChunk) chunks of the block
-    o.g = bstart + cstart;
-    o.left = blen - cstart < kChunk ? (int)(blen - cstart) : (int)kChunk;
-    return o;
-}
 
 // the terms a pass needs, by their index relative to `g`; outside [rlo, rhi] nobody needs them: zeros, no load.  Q == 3:
 // the lag terms c.re, c.im and q(x_j) of index g + r; Q == 1: q(x_j) alone
@@ -178,25 +165,6 @@ __device__ __forceinline__ Cand cand_combine(const Cand &a, const Cand &b, size_
     o.reserved = 0;
     return o;
 }
-__device__ __forceinline__ Cand cand_shfl_xor(const Cand &a, int mask)
-{
-    Cand o;
-    o.index = __shfl_xor(a.index, mask); o.first = __shfl_xor(a.first, mask);
-    o.p_re = __shfl_xor(a.p_re, mask); o.p_im = __shfl_xor(a.p_im, mask); o.r = __shfl_xor(a.r, mask); o.r_lag = __shfl_xor(a.r_lag, mask);
-    o.mn = __shfl_xor(a.mn, mask); o.reserved = 0;
-    return o;
-}
-// the workgroup's 256 records -> one, valid in thread 0; `lds` holds four records
-__device__ __forceinline__ Cand cand_block_reduce(Cand a, Cand *lds, size_t n)
-{
-#pragma unroll
-    for (int mask = 32; mask >= 1; mask >>= 1) a = cand_combine(a, cand_shfl_xor(a, mask), n);
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) a = cand_combine(cand_combine(lds[0], lds[1], n), cand_combine(lds[2], lds[3], n), n);
-    return a;
-}
-
 // ---- the chunk kernel -----------------------------------------------------------------------------------------------
 __device__ __forceinline__ long long floor_div(long long a, int w) { return a >= 0 ? a / w : -((-a + w - 1) / w); }
 
@@ -327,8 +295,8 @@ __global__ __launch_bounds__(kBlock) void mov_kernel(const Args a)
     static_assert(sizeof(double) * kCells >= 4 * sizeof(Peak), "the search records reuse EP[0]");
 
     const int tid = (int)threadIdx.x;
-    const Geo geo = geo_of(a.n, a.block, a.cpb);
-    const int W = a.window, left = geo.left;
+    const aeth::red::Geo geo = aeth::red::geo_of<kChunk>(a.n, a.block, a.cpb);
+    const int W = a.window, left = (int)geo.left;
     const long long g = (long long)geo.g, L = (long long)a.lag, H = (long long)(W - 1) + L;
 
     // windows up to kStageWindow: the samples the chunk needs, and their lag partners, once into LDS (consecutive lanes,
@@ -393,7 +361,8 @@ __global__ __launch_bounds__(kBlock) void mov_kernel(const Args a)
     });
     if constexpr (SEARCH) {
         best.mn = cand_pack(best.index == a.n ? __builtin_nanf("") : best_m, n_nan);
-        best = cand_block_reduce(best, reinterpret_cast<Cand *>(&EP[0][0]), a.n);
+        best = aeth::red::block_reduce(best, reinterpret_cast<Cand *>(&EP[0][0]),
+                                       [&](const Cand &p, const Cand &q) { return cand_combine(p, q, a.n); });
         if (tid == 0) a.rec[a.direct ? geo.b : blockIdx.x] = best;
     } else {
         for (int o = tid; o < left; o += kBlock) {
@@ -412,29 +381,9 @@ __global__ __launch_bounds__(kBlock) void mov_kernel(const Args a)
 __global__ __launch_bounds__(kBlock) void mov_fold_kernel(const Cand *__restrict__ in, size_t per, size_t total, size_t n, Cand *__restrict__ out)
 {
     __shared__ Cand lds[4];
-    const size_t first = (size_t)blockIdx.x * per;
-    const size_t cnt = total - first < per ? total - first : per;
-    Cand a = cand_none(n);
-    for (size_t r = threadIdx.x; r < cnt; r += kBlock) a = cand_combine(a, in[first + r], n);
-    a = cand_block_reduce(a, lds, n);
+    const Cand a = aeth::red::fold(in, per, total, cand_none(n), lds, [&](const Cand &p, const Cand &q) { return cand_combine(p, q, n); });
     if (threadIdx.x == 0) out[blockIdx.x] = a;
 }
-
-// how a call is cut: nb blocks of `block` samples (the last one short), cpb chunks in a full block, nwg workgroups
-struct Cut { size_t block, nb, cpb, nwg; };
-
-bool cut_of(size_t n, size_t block, Cut &c)
-{
-    c.block = block ? block : n;
-    c.nb = (n + c.block - 1) / c.block;
-    c.cpb = (c.block + kChunk - 1) / kChunk;
-    if (c.nb >= ((size_t)1 << 31) || c.cpb >= ((size_t)1 << 31)) return false;
-    const size_t last = n - (c.nb - 1) * c.block;
-    c.nwg = (c.nb - 1) * c.cpb + (last + kChunk - 1) / kChunk;
-    return c.nwg < ((size_t)1 << 31);
-}
-
-inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // what both device calls check behind their outputs, in this order, before any device work
 int check_call(int kind, size_t window, size_t lag, const aeth_cf32 *hist_dev, const aeth_cf32 *x_dev, size_t n)
@@ -522,12 +471,13 @@ int aeth_mov_exec(aeth_ctx *ctx, int kind, size_t window, size_t lag, const aeth
     int rc = check_call(kind, window, lag, hist_dev, x_dev, n); if (rc) return rc;
     AETH_REQUIRE(kind == AETH_MOV_LAG || !p_dev, AETH_E_ARG, "the power kind has no p plane (p_dev %p)", (void *)p_dev);
     AETH_REQUIRE(aeth::aligned8(p_dev), AETH_E_ALIGN, "p_dev %p not 8-byte aligned", (void *)p_dev);
-    AETH_REQUIRE(aligned4(r_dev) && aligned4(m_dev), AETH_E_ALIGN, "r_dev %p or m_dev %p not 4-byte aligned", (void *)r_dev, (void *)m_dev);
+    AETH_REQUIRE(aeth::aligned4(r_dev) && aeth::aligned4(m_dev), AETH_E_ALIGN, "r_dev %p or m_dev %p not 4-byte aligned", (void *)r_dev,
+                 (void *)m_dev);
     const Range in[2] = {{x_dev, n * sizeof(aeth_cf32), "x_dev"}, {hist_dev, history_of(kind, window, lag) * sizeof(aeth_cf32), "hist_dev"}};
     const Range out[3] = {{p_dev, n * sizeof(aeth_cf32), "p_dev"}, {r_dev, n * sizeof(float), "r_dev"}, {m_dev, n * sizeof(float), "m_dev"}};
     rc = check_overlap(in, 2, out, 3); if (rc) return rc;
     Cut c;
-    AETH_REQUIRE(cut_of(n, 0, c), AETH_E_UNSUPPORTED, "%zu samples need 2^31 workgroups or more", n);
+    AETH_REQUIRE(aeth::red::cut_of(n, 0, kChunk, c), AETH_E_UNSUPPORTED, "%zu samples need 2^31 workgroups or more", n);
 
     aeth::DeviceGuard dev_guard(ctx->device);
     const bool nt = aeth::streams_past_cache(n * sizeof(float2));
@@ -553,30 +503,23 @@ int aeth_mov_search(aeth_ctx *ctx, int kind, size_t window, size_t lag, double r
     AETH_REQUIRE(aeth::aligned8(peaks_dev) && aeth::aligned8(best_host), AETH_E_ALIGN, "peaks_dev %p or best_host %p not 8-byte aligned",
                  (void *)peaks_dev, (void *)best_host);
     Cut c;
-    AETH_REQUIRE(cut_of(n, block, c), AETH_E_UNSUPPORTED, "%zu samples in blocks of %zu need 2^31 workgroups or more", n, block);
+    AETH_REQUIRE(aeth::red::cut_of(n, block, kChunk, c), AETH_E_UNSUPPORTED, "%zu samples in blocks of %zu need 2^31 workgroups or more", n, block);
     const Range in[2] = {{x_dev, n * sizeof(aeth_cf32), "x_dev"}, {hist_dev, history_of(kind, window, lag) * sizeof(aeth_cf32), "hist_dev"}};
     const Range out[1] = {{peaks_dev, c.nb * sizeof(Peak), "peaks_dev"}};
     rc = check_overlap(in, 2, out, 1); if (rc) return rc;
 
-    aeth::DeviceGuard dev_guard(ctx->device);
-    const bool direct = c.cpb == 1;
-    const size_t nchunk = direct ? 0 : c.nwg;                        // slab: [chunk records][block records, unless the caller holds them]
-    rc = aeth::scratch_ensure(ctx, ctx->mov_slab, (nchunk + (peaks_dev ? 0 : c.nb)) * sizeof(Peak)); if (rc) return rc;
-    Cand *slab = static_cast<Cand *>(ctx->mov_slab.p);
-    Cand *blocks = peaks_dev ? reinterpret_cast<Cand *>(peaks_dev) : slab + nchunk;
-    aeth::HostIO io;
-    if (best_host) { rc = io.open(ctx, 0, sizeof(Peak)); if (rc) return rc; }    // the pinned bounce buffer
     const bool nt = aeth::streams_past_cache(n * sizeof(float2));
     Args a{reinterpret_cast<const float2 *>(x_dev), reinterpret_cast<const float2 *>(hist_dev), n, c.block, aeth::make_fastdiv((uint32_t)c.cpb),
-           (int)window, (unsigned)lag, r_min, threshold, nullptr, nullptr, nullptr, direct ? blocks : slab, direct ? 1 : 0};
-    hipStream_t s = aeth::ctx_stream(ctx);
-    if (kind == AETH_MOV_LAG) launch<AETH_MOV_LAG, OUT_SEARCH>(s, nt, (unsigned)c.nwg, a);
-    else launch<AETH_MOV_POWER, OUT_SEARCH>(s, nt, (unsigned)c.nwg, a);
-    if (!direct) hipLaunchKernelGGL(mov_fold_kernel, dim3((unsigned)c.nb), dim3(kBlock), 0, s, (const Cand *)slab, c.cpb, c.nwg, n, blocks);
-    if (best_host) hipLaunchKernelGGL(mov_fold_kernel, dim3(1), dim3(kBlock), 0, s, (const Cand *)blocks, c.nb, c.nb, n, static_cast<Cand *>(io.buf[1]));
-    AETH_HIP(hipGetLastError());
-    if (best_host) return io.get(best_host, 1, sizeof(Peak));
-    return AETH_OK;
+           (int)window, (unsigned)lag, r_min, threshold, nullptr, nullptr, nullptr, nullptr, 0};
+    return aeth::red::run_blocks(ctx, ctx->mov_slab, c, reinterpret_cast<Cand *>(peaks_dev), best_host,
+        [&](hipStream_t s, unsigned nwg, const Cand *in, size_t per, size_t total, Cand *out) {
+            hipLaunchKernelGGL(mov_fold_kernel, dim3(nwg), dim3(kBlock), 0, s, in, per, total, n, out);
+        },
+        [&](hipStream_t s, Cand *out, int direct) {
+            a.rec = out; a.direct = direct;
+            if (kind == AETH_MOV_LAG) launch<AETH_MOV_LAG, OUT_SEARCH>(s, nt, (unsigned)c.nwg, a);
+            else launch<AETH_MOV_POWER, OUT_SEARCH>(s, nt, (unsigned)c.nwg, a);
+        });
 }
 
 }  // extern "C"

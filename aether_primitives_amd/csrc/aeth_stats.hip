@@ -8,23 +8,22 @@
 //   sample i belongs to chunk i / 8192 (one workgroup), inside it to item (i % 8192) / 2, lane = item % 256,
 //   round = item / 256;
 //   a lane adds its 16 items in round order (first sample, then second), starting from 0;
-//   the 64 lanes of a wave combine by the xor butterfly 32, 16, 8, 4, 2, 1 (a + b == b + a bit for bit, so every lane
-//   holds the same value), the four waves as (w0 + w1) + (w2 + w3): one record per chunk, written to a slab;
-//   a second launch of ONE workgroup: lane t adds records t, t + 256, ... in that order, then the same butterfly and
-//   wave step.
+//   the 256 lanes' results become the chunk's record, written to a slab, and a second launch of ONE workgroup folds the
+//   chunk records from 0, both by THE TREE of aeth_reduce.h (a + b == b + a bit for bit).
 // Neither the CU count, nor the pointer's alignment (accesses are 16 bytes per lane at ANY 8-byte-aligned base: global
 // memory takes dword-aligned wide accesses, so there is no head / body / tail split to reorder anything), nor the
 // non-temporal choice enters.  min / max order by q (f64), ties to the lowest index: that choice is associative and
 // commutative, so it does not depend on the tree at all.
 #include "aeth_internal.h"
 #include "aeth_levels.h"
+#include "aeth_reduce.h"
 
 #include <cmath>
 #include <cstring>
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = aeth::red::kBlock;
 constexpr int kItems = 16;                                           // items (two samples, 16 bytes) per lane
 constexpr size_t kChunk = (size_t)kBlock * kItems * 2;               // 8192 samples, 64 KiB per workgroup
 constexpr unsigned long long kNone = ~0ull;
@@ -95,27 +94,6 @@ __device__ __forceinline__ Rec rec_combine(const Rec &a, const Rec &b)
     return r;
 }
 
-__device__ __forceinline__ Rec rec_shfl_xor(const Rec &a, int mask)
-{
-    Rec r;
-    r.sre = __shfl_xor(a.sre, mask); r.sim = __shfl_xor(a.sim, mask); r.sq = __shfl_xor(a.sq, mask);
-    r.nnan = __shfl_xor(a.nnan, mask);
-    r.minq = __shfl_xor(a.minq, mask); r.mini = __shfl_xor(a.mini, mask);
-    r.maxq = __shfl_xor(a.maxq, mask); r.maxi = __shfl_xor(a.maxi, mask);
-    return r;
-}
-
-// the workgroup's 256 partial results -> one, in the fixed order of the header; valid in thread 0
-__device__ __forceinline__ Rec rec_block_reduce(Rec a, Rec *lds)
-{
-#pragma unroll
-    for (int mask = 32; mask >= 1; mask >>= 1) a = rec_combine(a, rec_shfl_xor(a, mask));
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) a = rec_combine(rec_combine(lds[0], lds[1]), rec_combine(lds[2], lds[3]));
-    return a;
-}
-
 template <bool NT>
 __global__ __launch_bounds__(kBlock) void stats_partial_kernel(const float2 *__restrict__ x, size_t n, Rec *__restrict__ slab)
 {
@@ -158,16 +136,14 @@ __global__ __launch_bounds__(kBlock) void stats_partial_kernel(const float2 *__r
     a.sre = sre; a.sim = sim; a.sq = sq; a.nnan = nnan;
     a.minq = minq; a.mini = mini == ~0u ? kNone : base + mini;
     a.maxq = maxq; a.maxi = maxi == ~0u ? kNone : base + maxi;
-    a = rec_block_reduce(a, lds);
+    a = aeth::red::block_reduce(a, lds, rec_combine);
     if (threadIdx.x == 0) slab[blockIdx.x] = a;
 }
 
 __global__ __launch_bounds__(kBlock) void stats_final_kernel(const Rec *__restrict__ slab, size_t nrec, Rec *__restrict__ out)
 {
     __shared__ Rec lds[4];
-    Rec a = rec_identity();
-    for (size_t r = threadIdx.x; r < nrec; r += kBlock) a = rec_combine(a, slab[r]);
-    a = rec_block_reduce(a, lds);
+    const Rec a = aeth::red::fold(slab, nrec, nrec, rec_identity(), lds, rec_combine);
     if (threadIdx.x == 0) *out = a;
 }
 
@@ -260,7 +236,7 @@ int aeth_vec_levels(aeth_ctx *ctx, const aeth_cf32 *x_dev, size_t n, int kind, f
     if (n == 0) return AETH_OK;
     AETH_REQUIRE(x_dev && levels_dev, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned8(x_dev), AETH_E_ALIGN, "x not 8-byte aligned");
-    AETH_REQUIRE((reinterpret_cast<uintptr_t>(levels_dev) & 3u) == 0, AETH_E_ALIGN, "levels not 4-byte aligned");
+    AETH_REQUIRE(aeth::aligned4(levels_dev), AETH_E_ALIGN, "levels not 4-byte aligned");
     AETH_REQUIRE(!aeth::ranges_touch(x_dev, n * sizeof(aeth_cf32), levels_dev, n * sizeof(float)), AETH_E_ARG, "levels overlaps x");
     AETH_REQUIRE((n + 1) / 2 / kBlock < 0x7fffffffu, AETH_E_UNSUPPORTED, "%zu samples", n);
     aeth::DeviceGuard dev_guard(ctx->device);

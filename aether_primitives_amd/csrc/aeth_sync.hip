@@ -12,11 +12,8 @@
 //   a lane starts each sum from -0.0 (the identity of IEEE addition: the sum of ONE term is that term, sign of zero
 //   included) and adds the terms of its pairs in round order, first sample then second, then the odd last sample if it
 //   owns it: ascending index.  A term that does not exist (a lag term in front of the call without history) is skipped;
-//   the 64 lanes of a wave combine by the xor butterfly 32, 16, 8, 4, 2, 1 (a + b == b + a bit for bit, so every lane
-//   holds the same value), the four waves as (w0 + w1) + (w2 + w3): one record per chunk;
-//   a block of one chunk is done.  Otherwise one workgroup per block folds the chunk records: lane t adds records t,
-//   t + 256, ... in that order from -0.0, then the same butterfly and wave step;
-//   the total is the same fold over the block records, in one workgroup.
+//   the 256 lanes' sums become the chunk's record, the chunk records the block's, the block records the total by THE TREE
+//   of aeth_reduce.h (a + b == b + a bit for bit), every fold from -0.0; a block of one chunk is done with its chunk.
 // A record without terms is written as +0.0 sums (only the records handed out; chunk records keep the identity).
 // Neither the CU count, nor the pointer's alignment (16-byte buffer loads at ANY 8-byte-aligned base, so there is no
 // head / body / tail split), nor the non-temporal choice enters.
@@ -28,6 +25,7 @@
 #include "aeth_internal.h"
 #include "aeth_levels.h"
 #include "aeth_nco_core.h"
+#include "aeth_reduce.h"
 
 #include <cmath>
 
@@ -36,11 +34,13 @@ namespace {
 using aeth::FastDiv;
 using aeth::nco::Phasor;
 using aeth::nco::Words;
+using aeth::red::Cut;
+using aeth::red::Geo;
 
 typedef aeth_sync_record Rec;
 static_assert(sizeof(Rec) == 48, "record layout");
 
-constexpr int kBlock = 256;
+constexpr int kBlock = aeth::red::kBlock;
 constexpr int kItems = 8;                                            // 16-byte loads (two samples) per lane
 constexpr unsigned kChunk = kBlock * kItems * 2;                     // 4096 samples, 32 KiB per workgroup
 constexpr int kFar = 0x7ffffff0;                                     // an offset no descriptor here covers
@@ -76,24 +76,6 @@ __device__ __forceinline__ Rec rec_combine(const Rec &a, const Rec &b)
     r.re = a.re + b.re; r.im = a.im + b.im; r.mass = a.mass + b.mass;
     r.n = a.n + b.n; r.n_nonfinite = a.n_nonfinite + b.n_nonfinite; r.reserved = 0;
     return r;
-}
-__device__ __forceinline__ Rec rec_shfl_xor(const Rec &a, int mask)
-{
-    Rec r;
-    r.re = __shfl_xor(a.re, mask); r.im = __shfl_xor(a.im, mask); r.mass = __shfl_xor(a.mass, mask);
-    r.n = __shfl_xor((unsigned long long)a.n, mask); r.n_nonfinite = __shfl_xor((unsigned long long)a.n_nonfinite, mask);
-    r.reserved = 0;
-    return r;
-}
-// the workgroup's 256 partial results -> one, in the fixed order of the header; valid in thread 0
-__device__ __forceinline__ Rec rec_block_reduce(Rec a, Rec *lds)
-{
-#pragma unroll
-    for (int mask = 32; mask >= 1; mask >>= 1) a = rec_combine(a, rec_shfl_xor(a, mask));
-    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) a = rec_combine(rec_combine(lds[0], lds[1]), rec_combine(lds[2], lds[3]));
-    return a;
 }
 // a record that is handed out: no terms -> +0.0 sums
 __device__ __forceinline__ Rec rec_public(Rec a)
@@ -139,21 +121,6 @@ __device__ __forceinline__ void lag_term(Rec &acc, float xr, float xi, float pr,
     take(acc, ar * br + ai * bi, ai * br - ar * bi, aeth::level_q(a.re, a.im), live);
 }
 
-// where a workgroup works: block b, chunk k of it -> first sample of the call (g), samples (left)
-struct Geo { unsigned b; size_t g; unsigned left; };
-__device__ __forceinline__ Geo geo_of(size_t n, size_t block, const FastDiv &cpb)
-{
-    Geo o;
-    o.b = aeth::fdiv(blockIdx.x, cpb);
-    const unsigned k = blockIdx.x - o.b * cpb.d;
-    const size_t bstart = (size_t)o.b * block;
-    const size_t blen = n - bstart < block ? n - bstart : block;
-    const size_t cstart = (size_t)k * kChunk;                        // < blen: the grid holds ceil(blen / kChunk) chunks of the block
-    o.g = bstart + cstart;
-    o.left = blen - cstart < kChunk ? (unsigned)(blen - cstart) : kChunk;
-    return o;
-}
-
 template <bool NT> __device__ __forceinline__ f32x4 ld16(__amdgpu_buffer_rsrc_t rs, int off)
 {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, NT ? 2 : 0));
@@ -190,7 +157,7 @@ __global__ __launch_bounds__(kBlock) void sync_line_kernel(const float2 *__restr
                                                            Words base, Rec *__restrict__ out, int direct)
 {
     __shared__ Rec lds[4];
-    const Geo g = geo_of(n, block, cpb);
+    const Geo g = aeth::red::geo_of<kChunk>(n, block, cpb);
     const bool own_tail = (g.left & 1u) && threadIdx.x == (((g.left - 1) >> 1) & (kBlock - 1));
     f32x4 v[kItems];
     f32x2 t;
@@ -213,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void sync_line_kernel(const float2 *__restr
         if constexpr (!ZERO) w = word(g.left - 1);
         line_term<KIND, ZERO>(a, t.x, t.y, w, own_tail);
     }
-    a = rec_block_reduce(a, lds);
+    a = aeth::red::block_reduce(a, lds, rec_combine);
     write_record(a, out, g, direct);
 }
 
@@ -222,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void sync_lag_kernel(const float2 *__restri
                                                           size_t block, FastDiv cpb, size_t lag, Rec *__restrict__ out, int direct)
 {
     __shared__ Rec lds[4];
-    const Geo g = geo_of(n, block, cpb);
+    const Geo g = aeth::red::geo_of<kChunk>(n, block, cpb);
     const bool own_tail = (g.left & 1u) && threadIdx.x == (((g.left - 1) >> 1) & (kBlock - 1));
     f32x4 v[kItems], p[kItems];
     f32x2 t, pt;
@@ -259,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void sync_lag_kernel(const float2 *__restri
         lag_term<M>(a, v[i].z, v[i].w, p[i].z, p[i].w, live && s0 + 1 >= first);
     }
     lag_term<M>(a, t.x, t.y, pt.x, pt.y, own_tail && g.left - 1 >= first);
-    a = rec_block_reduce(a, lds);
+    a = aeth::red::block_reduce(a, lds, rec_combine);
     write_record(a, out, g, direct);
 }
 
@@ -267,26 +234,8 @@ __global__ __launch_bounds__(kBlock) void sync_lag_kernel(const float2 *__restri
 __global__ __launch_bounds__(kBlock) void sync_fold_kernel(const Rec *__restrict__ in, size_t per, size_t total, Rec *__restrict__ out)
 {
     __shared__ Rec lds[4];
-    const size_t first = (size_t)blockIdx.x * per;
-    const size_t cnt = total - first < per ? total - first : per;
-    Rec a = rec_identity();
-    for (size_t r = threadIdx.x; r < cnt; r += kBlock) a = rec_combine(a, in[first + r]);
-    a = rec_block_reduce(a, lds);
+    const Rec a = aeth::red::fold(in, per, total, rec_identity(), lds, rec_combine);
     if (threadIdx.x == 0) out[blockIdx.x] = rec_public(a);
-}
-
-// how a call is cut: nb blocks of `block` samples (the last one short), cpb chunks in a full block, nwg workgroups
-struct Cut { size_t block, nb, cpb, nwg; };
-
-bool cut_of(size_t n, size_t block, Cut &c)
-{
-    c.block = block ? block : n;
-    c.nb = (n + c.block - 1) / c.block;
-    c.cpb = (c.block + kChunk - 1) / kChunk;
-    if (c.nb >= ((size_t)1 << 31) || c.cpb >= ((size_t)1 << 31)) return false;
-    const size_t last = n - (c.nb - 1) * c.block;
-    c.nwg = (c.nb - 1) * c.cpb + (last + kChunk - 1) / kChunk;
-    return c.nwg < ((size_t)1 << 31);
 }
 
 // what both device calls check, in this order, before any device work
@@ -296,32 +245,21 @@ int check_call(const aeth_cf32 *hist_dev, size_t lag, const aeth_cf32 *x_dev, si
     AETH_REQUIRE(x_dev, AETH_E_ARG, "x is null");
     AETH_REQUIRE(aeth::aligned8(x_dev) && aeth::aligned8(hist_dev) && aeth::aligned8(rec_dev) && aeth::aligned8(total_host), AETH_E_ALIGN,
                  "pointer not 8-byte aligned");
-    AETH_REQUIRE(cut_of(n, block, c), AETH_E_UNSUPPORTED, "%zu samples in blocks of %zu need 2^31 workgroups or more", n, block);
+    AETH_REQUIRE(aeth::red::cut_of(n, block, kChunk, c), AETH_E_UNSUPPORTED, "%zu samples in blocks of %zu need 2^31 workgroups or more", n, block);
     AETH_REQUIRE(!aeth::ranges_touch(rec_dev, c.nb * sizeof(Rec), x_dev, n * sizeof(aeth_cf32)) &&
                  !aeth::ranges_touch(rec_dev, c.nb * sizeof(Rec), hist_dev, lag * sizeof(aeth_cf32)), AETH_E_ARG,
                  "the records overlap the input (or its history)");
     return AETH_OK;
 }
 
-// behind the chunk kernel: the per-block fold and the total; `launch(out, direct)` enqueues the chunk kernel
-template <class F>
-int run(aeth_ctx *ctx, const Cut &c, aeth_sync_record *rec_dev, aeth_sync_record *total_host, F launch)
+// behind the chunk kernel (`launch`): the per-block fold and the total
+template <class L>
+int run(aeth_ctx *ctx, const Cut &c, aeth_sync_record *rec_dev, aeth_sync_record *total_host, L launch)
 {
-    aeth::DeviceGuard dev_guard(ctx->device);
-    const bool direct = c.cpb == 1;
-    const size_t nchunk = direct ? 0 : c.nwg;                        // slab: [chunk records][block records, unless the caller holds them]
-    int rc = aeth::scratch_ensure(ctx, ctx->sync_slab, (nchunk + (rec_dev ? 0 : c.nb)) * sizeof(Rec)); if (rc) return rc;
-    Rec *slab = static_cast<Rec *>(ctx->sync_slab.p);
-    Rec *blocks = rec_dev ? rec_dev : slab + nchunk;
-    aeth::HostIO io;
-    if (total_host) { rc = io.open(ctx, 0, sizeof(Rec)); if (rc) return rc; }    // the pinned bounce buffer
-    hipStream_t s = aeth::ctx_stream(ctx);
-    launch(s, direct ? blocks : slab, direct ? 1 : 0);
-    if (!direct) hipLaunchKernelGGL(sync_fold_kernel, dim3((unsigned)c.nb), dim3(kBlock), 0, s, (const Rec *)slab, c.cpb, c.nwg, blocks);
-    if (total_host) hipLaunchKernelGGL(sync_fold_kernel, dim3(1), dim3(kBlock), 0, s, (const Rec *)blocks, c.nb, c.nb, static_cast<Rec *>(io.buf[1]));
-    AETH_HIP(hipGetLastError());
-    if (total_host) return io.get(total_host, 1, sizeof(Rec));
-    return AETH_OK;
+    return aeth::red::run_blocks(ctx, ctx->sync_slab, c, rec_dev, total_host,
+                                 [](hipStream_t s, unsigned nwg, const Rec *in, size_t per, size_t total, Rec *out) {
+                                     hipLaunchKernelGGL(sync_fold_kernel, dim3(nwg), dim3(kBlock), 0, s, in, per, total, out);
+                                 }, launch);
 }
 
 template <int KIND> auto line_kernel_of(bool nt, bool zero)

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import MovPeak, check
+from ._records import DeviceRecordArray, _vec, n_blocks   # noqa: F401  (n_blocks: public here)
 from .context import DeviceF32, DeviceVec
 
 LAG, POWER = 0, 1
@@ -31,42 +32,10 @@ def grid(kind, window):
     return _lib.load().aeth_mov_grid(int(kind), int(window))
 
 
-def n_blocks(n, block):
-    """records a search over n samples produces"""
-    n, block = int(n), int(block)
-    return -(-n // (block if block else max(n, 1)))
-
-
-class DevicePeaks:
+class DevicePeaks(DeviceRecordArray):
     """`count` records on the device, filled by `search_into` (stream-ordered, no wait)."""
 
-    def __init__(self, ctx, count):
-        self.ctx, self.n = ctx, int(count)
-        self.ptr = ctx.alloc(max(self.n, 1) * PEAK_DTYPE.itemsize)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr)
-                self.ptr = None
-        except Exception:
-            pass
-
-    def to_host(self):
-        out = np.empty(self.n, PEAK_DTYPE)
-        if self.n:
-            self.ctx.download(self.ptr, out)
-        return out
-
-    def _p(self):
-        return C.c_void_p(self.ptr)
-
-
-def _vec(ctx, x):
-    return x if isinstance(x, DeviceVec) else ctx.vec(x)
+    DTYPE = PEAK_DTYPE
 
 
 def _hist(ctx, hist, kind, window, lag):

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import SyncRecord, check
-from .context import DeviceVec
+from ._records import DeviceRecordArray, _vec, n_blocks   # noqa: F401  (n_blocks: public here)
 from .nco import _Words
 
 SQUARE, POW1, POW2, POW4, POW8 = 0, 1, 2, 4, 8
@@ -27,38 +27,10 @@ def chunk():
     return _lib.load().aeth_sync_chunk()
 
 
-def n_blocks(n, block):
-    """records a call over n samples produces"""
-    n, block = int(n), int(block)
-    return -(-n // (block if block else max(n, 1)))
-
-
-class DeviceRecords:
+class DeviceRecords(DeviceRecordArray):
     """`count` records on the device, filled by `line_into` / `lag_into` (stream-ordered, no wait)."""
 
-    def __init__(self, ctx, count):
-        self.ctx, self.n = ctx, int(count)
-        self.ptr = ctx.alloc(max(self.n, 1) * RECORD_DTYPE.itemsize)
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr)
-                self.ptr = None
-        except Exception:
-            pass
-
-    def to_host(self):
-        out = np.empty(self.n, RECORD_DTYPE)
-        if self.n:
-            self.ctx.download(self.ptr, out)
-        return out
-
-    def _p(self):
-        return C.c_void_p(self.ptr)
+    DTYPE = RECORD_DTYPE
 
 
 def _record(r):
@@ -68,10 +40,6 @@ def _record(r):
     if isinstance(r, complex):
         return SyncRecord(r.real, r.imag, 0.0, 0, 0, 0)
     return SyncRecord(float(r["re"]), float(r["im"]), float(r["mass"]), int(r["n"]), int(r["n_nonfinite"]), 0)
-
-
-def _vec(ctx, x):
-    return x if isinstance(x, DeviceVec) else ctx.vec(x)
 
 
 def line_into(ctx, x, kind, rec, words=None, position=0, block=0, total=False):
