@@ -82,6 +82,13 @@ constexpr int V_ALL = V_PRIO | V_XOR | V_SPREAD | V_DECIM | V_DEMOD | V_DM_BPSK 
 // cache-policy bits of the streamed accesses (aux operand of the buffer instructions: 1 = sc0, 2 = nt, 16 = sc1):
 // loads nt, stores nt + sc1 (tools/nt_modes.hip: 6.55 against 6.43 TB/s for nt alone)
 constexpr int kLoadAux = 2, kStoreAux = 18;
+// ... except a window's halo slots, whose lines a second workgroup (on another XCD) reads within the same round: the
+// last ov samples of a window are the first ov of its right neighbour's.  Plain (0) instead of nt: +3.2 % on the
+// headline with 20 and with 2000 steps, six alternating runs each (profiles/fir_head_bench.txt).  FETCH_SIZE does not
+// move (139.0 MB per launch before and after, profiles/r06_summary.json): it counts what L2 requests, in front of the
+// memory-side cache, so the gain is the second reader's requests being served there, not fewer of them.  sc1 (16) was
+// built, gives the same bits, and was not measured.
+constexpr int kHaloAux = 0;
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -92,6 +99,18 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ cf as_cf(u32x2 v) { return __builtin_bit_cast(cf, v); }
 __device__ __forceinline__ u32x2 as_u32x2(cf v) { return __builtin_bit_cast(u32x2, v); }
+
+// Slot m of a window through its descriptor.  The aux operand is an immediate and ov a run-time value, so "halo slot" is
+// a compile-time rule: the first and the last slot.  The halo is window elements [0, ov) and [hop, N): exact for
+// ov <= T (N = 2048 with up to 129 taps), a partial saving and no error when ov > T (200 taps: ov = 256, slots 1 and 14
+// keep the hint).  Frames (ov = 0) go through the same builds and lose the hint on these two slots as well.
+template <class C, bool NT, class RS>
+__device__ __forceinline__ cf load_slot(RS rs, int tid, int m)
+{
+    const int off = (tid + m * C::T) * 8;
+    if (m == 0 || m == C::P - 1) return as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, NT ? kHaloAux : 0));
+    return as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, NT ? kLoadAux : 0));
+}
 
 // one block's input window -> registers (slot m = window element tid + m*T)
 template <class C, bool NT>
@@ -111,7 +130,7 @@ __device__ __forceinline__ void load_window(cf (&x)[C::P], const FmiArgs &a, lon
             auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
             for (int m = 0; m < C::P; m++)
-                x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? kLoadAux : 0));
+                x[m] = load_slot<C, NT>(rs, tid, m);
             // (the window's oldest ov-nhist samples are zeroed when the window is consumed: doing it
             // here would put a wait for the load right behind its issue)
             return;
@@ -166,7 +185,7 @@ __device__ __forceinline__ void load_window_srd(cf (&x)[C::P], const FmiArgs &a,
     auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
     for (int m = 0; m < C::P; m++)
-        x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? kLoadAux : 0));
+        x[m] = load_slot<C, NT>(rs, tid, m);
 }
 
 // the same, slots [M0, M1) only (V_SPREAD: the window arrives in four instalments)
@@ -180,7 +199,7 @@ __device__ __forceinline__ void load_window_srd_part(cf (&x)[C::P], const FmiArg
     auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
     for (int m = M0; m < M1; m++)
-        x[m] = as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, (tid + m * C::T) * 8, 0, NT ? kLoadAux : 0));
+        x[m] = load_slot<C, NT>(rs, tid, m);
     __builtin_amdgcn_sched_barrier(0);
 }
 
