@@ -12,7 +12,7 @@ from ._lib import AetherError, LengthMismatch, load as _load
 
 _load()   # fail loudly at import time if the HIP library is not built
 
-from .context import (Context, DeviceVec, DeviceF32, HostVec, VecStats,  # noqa: E402
+from .context import (Context, DeviceVec, DeviceF32, DeviceF64, HostVec, VecStats,  # noqa: E402
                       LEVEL_NORM, LEVEL_DB, LEVEL_POWER_DB)
 from .fft import Scale, HipFft, SIGN_REF_FWD, SIGN_REF_BWD  # noqa: E402
 from .fir import Fir                                      # noqa: E402
@@ -44,7 +44,7 @@ from . import pool                                        # noqa: E402
 from . import pipeline                                    # noqa: E402
 from .evm import assert_evm, evm_db                       # noqa: E402
 
-__all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "DeviceF32", "HostVec", "VecStats", "LEVEL_NORM",
+__all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "DeviceF32", "DeviceF64", "HostVec", "VecStats", "LEVEL_NORM",
            "LEVEL_DB", "LEVEL_POWER_DB", "Scale", "HipFft",
            "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "Corr", "CorrPeak", "sampling", "modulation", "noise", "sequence", "Sequence",
            "lte_gold", "chan", "Channelizer", "synth", "Synthesizer", "resamp", "Resampler", "arb", "ArbResampler", "step_word",

@@ -187,6 +187,11 @@ PROTOTYPES = {
     "aeth_chan_exec": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, vp, sz]),
     "aeth_chan_exec_levels": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, i32, i32, vp, sz]),
     "aeth_chan_prototype": (i32, [i32, sz, sz, vp]),
+    "aeth_vec_frame_sums": (i32, [vp, vp, sz, sz, sz, sz, vp, vp, sz]),
+    "aeth_chan_exec_sums": (i32, [vp, vp, vp, sz, u64, i32, i32, f32, i32, sz, i32, vp, vp, sz]),
+    "aeth_chan_sums_chunk": (sz, [vp]),
+    "aeth_chan_sums_fused": (i32, [vp]),
+    "aeth_vec_sum_levels": (i32, [vp, vp, sz, C.c_double, i32, vp]),
     "aeth_synth_create": (i32, [vp, vp, sz, sz, sz, i32, sz, pvp]),
     "aeth_synth_destroy": (i32, [vp]),
     "aeth_synth_channels": (sz, [vp]),

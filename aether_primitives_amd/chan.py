@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .context import DeviceF32, DeviceVec, LEVEL_NORM
+from .context import DeviceF32, DeviceF64, DeviceVec, LEVEL_NORM
 from .fft import SIGN_REF_FWD, Scale
 
 PHASE_FRAME, PHASE_STREAM = 0, 1
@@ -117,3 +117,29 @@ class Channelizer(_Bank):
         check(self._lib.aeth_chan_exec_levels(self.h, hp, x._p(), x.n, int(first_frame), sign, s.kind, s.x, 1 if mirror else 0,
                                               int(kind), out._p(), out.n))
         return out
+
+    @property
+    def sums_chunk(self):
+        """frames per chunk of `sums` (the launch geometry: the order of its additions)"""
+        return self._lib.aeth_chan_sums_chunk(self.h)
+
+    @property
+    def sums_fused(self):
+        """does `sums` without general=True take the one-kernel route?"""
+        return bool(self._lib.aeth_chan_sums_fused(self.h))
+
+    def sums(self, x, hist=None, first_frame=0, sign=SIGN_REF_FWD, s=Scale.NONE, mirror=False, block=0, general=False,
+             want=("sum", "max")):
+        """averaged spectra: fold, transform, vec_mirror if `mirror`, then per bin the sum and the maximum of q = |X|^2
+        (f64) over rows of `block` frames (0: one row over the whole call) -> (sum, max) as DeviceF64 of rows * channels
+        values; a plane that `want` does not name is None.  Welch's periodogram is sum / frames, the max plane is a
+        spectrum analyser's max hold.  general=True never takes the one-kernel route (same bytes)."""
+        x, hist, hp = self._args(x, hist)
+        frames, block = self.frames(x.n), int(block)
+        rows = -(-frames // block) if 0 < block < frames else 1
+        n_out = rows * self.channels
+        sm = DeviceF64(self.ctx, n_out) if "sum" in want else None
+        mx = DeviceF64(self.ctx, n_out) if "max" in want else None
+        check(self._lib.aeth_chan_exec_sums(self.h, hp, x._p(), x.n, int(first_frame), sign, s.kind, s.x, 1 if mirror else 0, block,
+                                            1 if general else 0, sm._p() if sm else None, mx._p() if mx else None, n_out))
+        return sm, mx

@@ -131,6 +131,29 @@ class Context:
     def empty(self, n):
         return DeviceVec(self, n)
 
+    # ---- averaged spectra (aeth_vec_frame_sums / aeth_vec_sum_levels; no body in the reference) ----
+    def frame_sums(self, vec, len, block=0, chunk=32, want=("sum", "max")):
+        """`vec` as frames of `len` samples: the per-column sum and maximum of q = re^2 + im^2 (f64) over rows of `block`
+        frames (0: one row over the whole call), frames added in chunks of `chunk` in ascending order -> (sum, max) as
+        DeviceF64 of rows * len values; a plane that `want` does not name is None."""
+        if not isinstance(vec, DeviceVec):
+            vec = self.vec(vec)
+        ln, block = int(len), int(block)
+        frames = vec.n // ln if ln else 0
+        rows = -(-frames // block) if 0 < block < frames else 1
+        s = DeviceF64(self, rows * ln) if "sum" in want else None
+        m = DeviceF64(self, rows * ln) if "max" in want else None
+        check(self._lib.aeth_vec_frame_sums(self.h, vec._p(), vec.n, ln, block, int(chunk), s._p() if s else None, m._p() if m else None,
+                                            rows * ln))
+        return s, m
+
+    def sum_levels(self, plane, count, kind=LEVEL_NORM, out=None):
+        """what a plot draws of a plane: the level (LEVEL_*) of q / count -> DeviceF32.  `count` is the number of frames
+        of a row for a sum plane, 1 for a max plane."""
+        out = DeviceF32(self, plane.n) if out is None else out
+        check(self._lib.aeth_vec_sum_levels(self.h, plane._p(), plane.n, float(count), int(kind), out._p()))
+        return out
+
     # ---- events (bench) ----
     def event(self):
         return Event(self)
@@ -191,6 +214,42 @@ class DeviceF32:
 
     def to_host(self):
         out = np.empty(self.n, np.float32)
+        if self.n:
+            self.ctx.download(self.ptr, out)
+        return out
+
+    def _p(self):
+        return C.c_void_p(self.ptr)
+
+
+class DeviceF64:
+    """Device-resident `[f64]`: the sum and max planes of averaged spectra."""
+
+    def __init__(self, ctx, n, ptr=None, offset=0, owner=None):
+        self.ctx, self.n, self._owner = ctx, int(n), owner
+        if ptr is None:
+            self._base = ctx.alloc(max(self.n, 1) * 8)
+            self.ptr, self._owns = self._base, True
+        else:
+            self._base, self.ptr, self._owns = ptr, ptr + offset * 8, False
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        try:
+            if self._owns and self._base and self.ctx.h:
+                self.ctx.free(self._base)
+                self._base = None
+        except Exception:
+            pass
+
+    def slice(self, start, stop):
+        assert 0 <= start <= stop <= self.n
+        return DeviceF64(self.ctx, stop - start, ptr=self.ptr, offset=start, owner=self)
+
+    def to_host(self):
+        out = np.empty(self.n, np.float64)
         if self.n:
             self.ctx.download(self.ptr, out)
         return out

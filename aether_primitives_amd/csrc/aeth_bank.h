@@ -143,3 +143,6 @@ int chan_launch_fold(const Bank &b, bool stream, const aeth_cf32 *hist, const ae
 
 }  // namespace bank
 }  // namespace aeth
+
+// the analysis bank's object: its calls are in aeth_chan.hip, its averaged spectra in aeth_spec.hip
+struct aeth_chan : aeth::bank::Bank {};

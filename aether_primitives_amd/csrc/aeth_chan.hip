@@ -145,8 +145,6 @@ template <int CW, bool NT> ChanKernel ring_kernel(unsigned P)
 
 }  // namespace
 
-struct aeth_chan : Bank {};
-
 bool aeth::bank::chan_ring(const Bank &b) { return b.D == b.M && b.P <= kRingMaxP; }
 size_t aeth::bank::chan_tile(const Bank &b) { return chan_ring(b) ? ring_tile(b.P) : gen_tile(b.M); }
 

@@ -56,7 +56,8 @@ struct aeth_ctx {
     //   corr_slab   per-wave and per-workgroup records of aeth_corr_search (aeth_fir.hip)
     //   sync_slab   [chunk records][block records] of aeth_sync_line / aeth_sync_lag (aeth_sync.hip), and
     //   mov_slab    the same of aeth_mov_search (aeth_mov.hip): the layout is aeth::red::run_blocks' (aeth_reduce.h)
-    aeth::DevScratch stage[2], stats_slab, corr_slab, sync_slab, mov_slab;
+    //   spec_slab   [chunk sums][chunk maxima] of aeth_vec_frame_sums / aeth_chan_exec_sums (aeth_spec.hip)
+    aeth::DevScratch stage[2], stats_slab, corr_slab, sync_slab, mov_slab, spec_slab;
     // small host-slice calls: two pinned, device-visible bounce buffers (aeth::HostIO)
     void *bounce[2] = {nullptr, nullptr};
     // plans of the one-shot vec_fft / vec_ifft (aeth_fft.hip: fft_cache_get), most recently used first
@@ -95,9 +96,9 @@ int scratch_ensure(aeth_ctx *ctx, DevScratch &s, size_t bytes, bool slack = true
 // aeth_ctx_destroy does not)
 hipError_t scratch_release(DevScratch &s);
 // every scratch buffer of the context
-inline std::array<DevScratch *, 6> ctx_scratch(aeth_ctx *ctx)
+inline std::array<DevScratch *, 7> ctx_scratch(aeth_ctx *ctx)
 {
-    return {&ctx->stage[0], &ctx->stage[1], &ctx->stats_slab, &ctx->corr_slab, &ctx->sync_slab, &ctx->mov_slab};
+    return {&ctx->stage[0], &ctx->stage[1], &ctx->stats_slab, &ctx->corr_slab, &ctx->sync_slab, &ctx->mov_slab, &ctx->spec_slab};
 }
 // ensure staging slot `i` holds >= bytes of device memory (an unused slot still gets 16 bytes)
 inline int ctx_stage(aeth_ctx *ctx, int i, size_t bytes) { return scratch_ensure(ctx, ctx->stage[i], bytes ? bytes : 16); }
@@ -123,9 +124,9 @@ struct HostIO {
 };
 
 // Tuning knobs: environment integers that are consulted ONLY when the process was started with AETH_TUNING=1; a
-// normal run never reads them.  libaether_hip.so carries the seven that choose between SHIPPED behaviours, all
+// normal run never reads them.  libaether_hip.so carries the eight that choose between SHIPPED behaviours, all
 // documented in include/aether_hip.h ("Tuning knobs"): AETH_FIR_GRID_FIRST, AETH_FIR_GRID_CHAINED, AETH_FIR_SPREAD,
-// AETH_NT, AETH_PIPE_THREADS, AETH_PIPE_MIXED, AETH_SYNC_SPIN_US.
+// AETH_NT, AETH_PIPE_THREADS, AETH_PIPE_MIXED, AETH_SYNC_SPIN_US, AETH_SPEC_SLICE_KIB.
 int tuning_int(const char *name, int dflt);
 // Lab knobs (tools/tune_*.py, prime_route.py, vs_rocfft.py sweeps): routes and shapes that were measured and not
 // kept.  They exist only in the lab build (`make LAB=1` -> lib/libaether_hip_lab.so, -DAETH_LAB=1); in the product

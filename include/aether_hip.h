@@ -95,7 +95,9 @@ enum { AETH_SIGN_REF_FWD = +1, AETH_SIGN_REF_BWD = -1 };
  *                          cgroup CPU quota --, 2..12)
  *   AETH_PIPE_MIXED        1: a pageable input next to a pinned output downloads directly into the caller's memory
  *                          (default 0: both sides staged -- the mixed form measured 2.4 x slower downloads)
- *   AETH_SYNC_SPIN_US      how long aeth_ctx_sync polls both queues before it blocks (default 2000) */
+ *   AETH_SYNC_SPIN_US      how long aeth_ctx_sync polls both queues before it blocks (default 2000)
+ *   AETH_SPEC_SLICE_KIB    KiB of spectrum the general route of aeth_chan_exec_sums keeps at a time (default 65536; the
+ *                          result does not depend on it) */
 AETH_API const char *aeth_last_error(void);
 AETH_API int aeth_version(void);                     /* 0x00MMmmpp */
 AETH_API int aeth_device_count(int *count);
@@ -514,6 +516,65 @@ AETH_API int aeth_chan_exec_levels(aeth_chan *chan, const aeth_cf32 *hist_dev, c
  *                 divided by its f64 sum (unit DC gain); L = 1 gives 1
  * A bad kind or a zero size: AETH_E_ARG. */
 AETH_API int aeth_chan_prototype(int kind, size_t channels, size_t taps_per_channel, float *out_host);
+
+/* ---- averaged spectra: per-bin power sums and max hold over frames (no body in the reference) ---- */
+/* The reference's `waterfall` (src/util/plot.rs:46-68) keeps the level of every bin of every frame.  Welch's averaged
+ * periodogram and the max-hold trace of a spectrum analyser keep ONE row of `len` numbers per `block` frames; the
+ * reduction over the frames is done here in f64, in an order that is part of the contract.
+ *
+ * Frames m = 0 .. F - 1 of len = M bins; q_m[k] = q(X_m[k]) = (double)re * re + (double)im * im of the bin (one f64
+ * rounding, as for aeth_vec_stats) exactly as aeth_chan_exec / aeth_fft_exec would have stored it: scaled, and (where a
+ * call has a `mirror` argument and it is not 0) after vec_mirror of the frame.
+ *   rows    block = B frames per output row, 0 (or more than F) means one row over the whole call.  R = ceil(F / B); row r
+ *           covers frames [r B, min(F, (r + 1) B)).
+ *   chunks  a row is cut into chunks of C >= 1 frames counted from the row's first frame; the last chunk of a row may
+ *           be short.
+ *   sum     a chunk's sum starts from its first frame's q and adds the following frames' q in ascending order; the row's
+ *           sum starts from chunk 0's sum and adds the following chunk sums in ascending order.  Every addition is one f64
+ *           rounding.  NaN and +inf are carried the ordinary way.
+ *   max     best = -inf; best = q > best ? q : best over the row's frames: a NaN q never enters, a column of NaNs gives
+ *           -inf.  The rule is associative and commutative, so its tree is free.
+ * The bytes of both planes are a function of the frames, B and C only: not of the CU count, pointer alignment, cache
+ * policy (AETH_NT), which planes are requested, or the route taken.  A stream cut at a multiple of B frames and continued
+ * with history gives the same rows.  There are no atomics; chunk results live in a scratch buffer of the context that
+ * aeth_ctx_trim releases, and go straight to the caller's planes when a row is one chunk.
+ *
+ * Not built: a min-hold plane, exponential averaging, a one-kernel route for P > 1 or the stream phase, an
+ * aeth_stream_op kind, host-slice flavours. */
+enum { AETH_SUMS_GENERAL = 1 };          /* aeth_chan_exec_sums flag: never take the fused route (verification, measurement) */
+/* No body in the reference (src/util/plot.rs:46-68 keeps every frame): the reduction alone over F = n / len frames of
+ * cf32 in device memory, chunk = C.  sum_dev / max_dev: R * len doubles each, either may be NULL, not both; n_out ==
+ * R * len.  A lane owns two adjacent columns (16-byte loads) or, for an odd len or a base that is only 8-byte aligned, one
+ * column (8-byte loads).  Everything is refused before any device work: NULL ctx, frames or both planes AETH_E_ARG; n == 0,
+ * len == 0, n not a multiple of len, chunk == 0 or a wrong n_out AETH_E_LEN; pointers not 8-byte aligned AETH_E_ALIGN; a plane
+ * that overlaps the input or the other plane AETH_E_ARG.  Ordered on the context's in-order stream; does not wait. */
+AETH_API int aeth_vec_frame_sums(aeth_ctx *ctx, const aeth_cf32 *frames_dev, size_t n, size_t len, size_t block, size_t chunk,
+                                 double *sum_dev, double *max_dev, size_t n_out);
+/* No body in the reference (src/util/plot.rs:46-68): the frames of aeth_chan_exec -- same framing, history, sign, Scale and
+ * checks as aeth_chan_exec_levels -- reduced as above with C = aeth_chan_sums_chunk(chan); n_out == R * M.  By contract
+ * byte-identical to aeth_chan_exec (then aeth_vec_mirror_frames if mirror != 0) followed by aeth_vec_frame_sums with that
+ * chunk.  Two routes, the same bytes:
+ *   fused    power-of-two M = 512 .. 4096 with ntaps == M and rot = 0 (AETH_CHAN_PHASE_FRAME, or hop == M): one kernel --
+ *            window, register transform, q and the f64 accumulation per chunk -- plus the row fold: 8 bytes read per
+ *            input sample, the spectrum is never written.
+ *   general  every other (M, P, D), phase mode and plan route aeth_chan_create accepts (smaller power-of-two M included),
+ *            and every shape under AETH_SUMS_GENERAL: fold, transform, chunk sums in slices of whole chunks through a
+ *            bounded scratch, then the row fold.
+ * flags: AETH_SUMS_GENERAL or 0; unknown bits AETH_E_ARG. */
+AETH_API int aeth_chan_exec_sums(aeth_chan *chan, const aeth_cf32 *hist_dev, const aeth_cf32 *in_dev, size_t n,
+                                 uint64_t first_frame, int sign, int scale_kind, float x, int mirror, size_t block, int flags,
+                                 double *sum_dev, double *max_dev, size_t n_out);
+/* No body in the reference: the frames per chunk of aeth_chan_exec_sums, like aeth_chan_tile: the launch geometry, for
+ * tests that want to cross its edges.  A function of M alone (16 Ki bins: 8 .. 32 frames); 0 for NULL. */
+AETH_API size_t aeth_chan_sums_chunk(const aeth_chan *chan);
+/* No body in the reference: 1 if aeth_chan_exec_sums without AETH_SUMS_GENERAL takes the one-kernel route. */
+AETH_API int aeth_chan_sums_fused(const aeth_chan *chan);
+/* No body in the reference (util/plot.rs:65,127 takes the level of one bin): what a plot draws of a plane.
+ * qbar = q_dev[i] / count (one f64 division), then the level formulas of aeth_vec_levels applied to qbar:
+ *   NORM (float)sqrt(qbar); DB (float)(10 log10((double)(float)sqrt(qbar))); POWER_DB (float)(10 log10(qbar)).
+ * count is the number of frames of a row for the sum plane, 1 for the max plane; it must be finite and > 0 (AETH_E_ARG).
+ * n == 0 -> AETH_OK without a launch; q_dev 8-byte, levels_dev 4-byte aligned (AETH_E_ALIGN); no overlap (AETH_E_ARG). */
+AETH_API int aeth_vec_sum_levels(aeth_ctx *ctx, const double *q_dev, size_t n, double count, int level_kind, float *levels_dev);
 
 /* ---- polyphase synthesis filter bank (no body in the reference) -------------------------------- */
 /* The transpose of aeth_chan: what puts a stream back together after aeth_chan_exec took it apart (the reference only

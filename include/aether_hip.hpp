@@ -102,6 +102,40 @@ private:
     size_t n_ = 0;
 };
 
+// device-resident [f64]: the sum and max planes of averaged spectra (aeth_vec_frame_sums, aeth_chan_exec_sums)
+class DeviceF64 {
+public:
+    DeviceF64(Context &ctx, size_t n) : ctx_(&ctx), n_(n)
+    {
+        void *p = nullptr;
+        check(aeth_dev_alloc(ctx.get(), (n ? n : 1) * sizeof(double), &p));
+        p_ = static_cast<double *>(p);
+    }
+    ~DeviceF64() { if (p_) aeth_dev_free(ctx_->get(), p_); }
+    DeviceF64(const DeviceF64 &) = delete;
+    DeviceF64 &operator=(const DeviceF64 &) = delete;
+    DeviceF64(DeviceF64 &&o) noexcept : ctx_(o.ctx_), p_(o.p_), n_(o.n_) { o.p_ = nullptr; }
+    size_t len() const { return n_; }
+    double *ptr() const { return p_; }
+    std::vector<double> to_host() const
+    {
+        std::vector<double> h(n_);
+        check(aeth_download(ctx_->get(), h.data(), p_, n_ * sizeof(double)));
+        return h;
+    }
+    // what a plot draws of the plane: the level of q / count (count: the frames of a row for a sum plane, 1 for a max plane)
+    DeviceF32 sum_levels(double count, Level kind = Level::Norm) const
+    {
+        DeviceF32 out(*ctx_, n_);
+        check(aeth_vec_sum_levels(ctx_->get(), p_, n_, count, static_cast<int>(kind), out.ptr()));
+        return out;
+    }
+private:
+    Context *ctx_;
+    double *p_ = nullptr;
+    size_t n_ = 0;
+};
+
 // ---- trait VecOps, device-resident receiver (src/vecops.rs:39-89) ------------------
 class DeviceVec {
 public:
@@ -162,6 +196,13 @@ public:
         DeviceF32 out(*ctx_, n_);
         check(aeth_vec_levels(c(), p_, n_, static_cast<int>(kind), out.ptr(), out.len()));
         return out;
+    }
+    // *this as frames of `len` samples: per-column sums and maxima of q over rows of `block` frames (0: one row), added
+    // in chunks of `chunk` frames (aeth_vec_frame_sums); a null plane is not computed
+    void frame_sums(size_t len, size_t block, size_t chunk, DeviceF64 *sum, DeviceF64 *max) const
+    {
+        const DeviceF64 *any = sum ? sum : max;
+        check(aeth_vec_frame_sums(c(), p_, n_, len, block, chunk, sum ? sum->ptr() : nullptr, max ? max->ptr() : nullptr, any ? any->len() : 0));
     }
     inline DeviceVec &vec_fft(Scale s);                    // fresh plan (src/vecops.rs:185-189)
     inline DeviceVec &vec_ifft(Scale s);
@@ -498,6 +539,16 @@ public:
         check(aeth_chan_exec_levels(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), first_frame, sign, s.kind, s.x, mirror ? 1 : 0,
                                     kind, out.ptr(), out.len()));
         return out;
+    }
+    // averaged spectra: per-bin sums and maxima of q over rows of `block` frames (0: one row); a null plane is not computed
+    size_t sums_chunk() const { return aeth_chan_sums_chunk(h_); }
+    bool sums_fused() const { return aeth_chan_sums_fused(h_) != 0; }
+    void sums(const DeviceVec &x, Scale s, DeviceF64 *sum, DeviceF64 *max, size_t block = 0, bool mirror = false, const DeviceVec *hist = nullptr,
+              uint64_t first_frame = 0, int sign = AETH_SIGN_REF_FWD, bool general = false)
+    {
+        const DeviceF64 *any = sum ? sum : max;
+        check(aeth_chan_exec_sums(h_, hist ? hist->ptr() : nullptr, x.ptr(), x.len(), first_frame, sign, s.kind, s.x, mirror ? 1 : 0, block,
+                                  general ? AETH_SUMS_GENERAL : 0, sum ? sum->ptr() : nullptr, max ? max->ptr() : nullptr, any ? any->len() : 0));
     }
     aeth_chan *get() const { return h_; }
 

@@ -1,7 +1,7 @@
 //! `extern "C"` declarations: one to one with include/aether_hip.h.
 #![allow(non_camel_case_types)]
 use aether_primitives::cf32;
-use std::os::raw::{c_char, c_float, c_int, c_uint, c_void};
+use std::os::raw::{c_char, c_double, c_float, c_int, c_uint, c_void};
 
 #[repr(C)] pub struct aeth_ctx { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_fft { _p: [u8; 0] }
@@ -96,6 +96,7 @@ pub const AETH_SCALE_X: c_int = 3;
 pub const AETH_SIGN_REF_FWD: c_int = 1;
 pub const AETH_SIGN_REF_BWD: c_int = -1;
 pub const AETH_OFDM_GENERAL: c_int = 1;
+pub const AETH_SUMS_GENERAL: c_int = 1;
 pub const AETH_OFDM_EQ_ZF: c_int = 0;
 pub const AETH_OFDM_EQ_MMSE: c_int = 1;
 pub const AETH_OFDM_EQ_MATCHED: c_int = 2;
@@ -227,6 +228,16 @@ extern "C" {
                                  sign: c_int, scale_kind: c_int, x: c_float, mirror: c_int, level_kind: c_int,
                                  levels_dev: *mut c_float, n_levels: usize) -> c_int;
     pub fn aeth_chan_prototype(kind: c_int, channels: usize, taps_per_channel: usize, out_host: *mut c_float) -> c_int;
+    // averaged spectra: per-bin power sums and max hold over frames
+    pub fn aeth_vec_frame_sums(ctx: *mut aeth_ctx, frames_dev: *const cf32, n: usize, len: usize, block: usize, chunk: usize,
+                               sum_dev: *mut c_double, max_dev: *mut c_double, n_out: usize) -> c_int;
+    pub fn aeth_chan_exec_sums(chan: *mut aeth_chan, hist_dev: *const cf32, in_dev: *const cf32, n: usize, first_frame: u64, sign: c_int,
+                               scale_kind: c_int, x: c_float, mirror: c_int, block: usize, flags: c_int, sum_dev: *mut c_double,
+                               max_dev: *mut c_double, n_out: usize) -> c_int;
+    pub fn aeth_chan_sums_chunk(chan: *const aeth_chan) -> usize;
+    pub fn aeth_chan_sums_fused(chan: *const aeth_chan) -> c_int;
+    pub fn aeth_vec_sum_levels(ctx: *mut aeth_ctx, q_dev: *const c_double, n: usize, count: c_double, level_kind: c_int,
+                               levels_dev: *mut c_float) -> c_int;
     pub fn aeth_synth_create(ctx: *mut aeth_ctx, proto_host: *const c_float, ntaps: usize, channels: usize, hop: usize, phase: c_int,
                              max_frames: usize, out: *mut *mut aeth_synth) -> c_int;
     pub fn aeth_synth_destroy(synth: *mut aeth_synth) -> c_int;

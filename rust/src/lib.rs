@@ -126,6 +126,29 @@ impl<'c> DeviceF32<'c> {
 }
 impl<'c> Drop for DeviceF32<'c> { fn drop(&mut self) { unsafe { aeth_dev_free(self.ctx.h, self.p as *mut c_void); } } }
 
+/// Device-resident `[f64]`: the sum and max planes of averaged spectra (aeth_vec_frame_sums, aeth_chan_exec_sums).
+pub struct DeviceF64<'c> { ctx: &'c Context, p: *mut f64, n: usize }
+impl<'c> DeviceF64<'c> {
+    pub fn new(ctx: &'c Context, n: usize) -> DeviceF64<'c> {
+        let mut p: *mut c_void = ptr::null_mut();
+        check(unsafe { aeth_dev_alloc(ctx.h, n.max(1) * 8, &mut p) });
+        DeviceF64 { ctx, p: p as *mut f64, n }
+    }
+    pub fn len(&self) -> usize { self.n }
+    pub fn to_vec(&self) -> Vec<f64> {
+        let mut v = vec![0f64; self.n];
+        check(unsafe { aeth_download(self.ctx.h, v.as_mut_ptr() as *mut c_void, self.p as *const c_void, self.n * 8) });
+        v
+    }
+    /// what a plot draws of the plane: the level of q / count (the frames of a row for a sum plane, 1 for a max plane)
+    pub fn sum_levels(&self, count: f64, kind: Level) -> DeviceF32<'c> {
+        let out = DeviceF32::new(self.ctx, self.n);
+        check(unsafe { aeth_vec_sum_levels(self.ctx.h, self.p, self.n, count, kind as i32, out.p) });
+        out
+    }
+}
+impl<'c> Drop for DeviceF64<'c> { fn drop(&mut self) { unsafe { aeth_dev_free(self.ctx.h, self.p as *mut c_void); } } }
+
 /// Device-resident `[cf32]` with the `VecOps` method set (src/vecops.rs:39-89).
 pub struct DeviceVec<'c> { ctx: &'c Context, p: *mut cf32, n: usize }
 impl<'c> DeviceVec<'c> {
@@ -152,6 +175,13 @@ impl<'c> DeviceVec<'c> {
         let out = DeviceF32::new(self.ctx, self.n);
         check(unsafe { aeth_vec_levels(self.ctx.h, self.p, self.n, kind as i32, out.p, out.n) });
         out
+    }
+    /// `self` as frames of `len` samples: per-column sums and maxima of q over rows of `block` frames (0: one row), added
+    /// in chunks of `chunk` frames (aeth_vec_frame_sums); a plane that is None is not computed
+    pub fn frame_sums(&self, len: usize, block: usize, chunk: usize, sum: Option<&mut DeviceF64>, max: Option<&mut DeviceF64>) {
+        let n_out = sum.as_ref().map(|v| v.n).or(max.as_ref().map(|v| v.n)).unwrap_or(0);
+        check(unsafe { aeth_vec_frame_sums(self.ctx.h, self.p, self.n, len, block, chunk, sum.map_or(ptr::null_mut(), |v| v.p),
+                                           max.map_or(ptr::null_mut(), |v| v.p), n_out) });
     }
     pub fn vec_scale(&mut self, s: f32) -> &mut Self { check(unsafe { aeth_vec_scale(self.ctx.h, self.p, self.n, s) }); self }
     pub fn vec_mul(&mut self, o: &DeviceVec) -> &mut Self { check(unsafe { aeth_vec_mul(self.ctx.h, self.p, self.n, o.p, o.n) }); self }
@@ -298,6 +328,19 @@ impl<'c> Channelizer<'c> {
         let (kind, xs) = scale_args(s);
         check(unsafe { aeth_chan_exec(self.h, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n, first_frame,
                                       AETH_SIGN_REF_FWD, kind, xs, out.p, out.n) });
+    }
+    /// frames per chunk of `sums` (the launch geometry) and whether it takes the one-kernel route
+    pub fn sums_chunk(&self) -> usize { unsafe { aeth_chan_sums_chunk(self.h) } }
+    pub fn sums_fused(&self) -> bool { unsafe { aeth_chan_sums_fused(self.h) != 0 } }
+    /// averaged spectra: per-bin sums and maxima of q over rows of `block` frames (0: one row); a plane that is None is not
+    /// computed; `general`: never the one-kernel route
+    pub fn sums(&mut self, x: &DeviceVec, hist: Option<&DeviceVec>, first_frame: u64, s: Scale, mirror: bool, block: usize, general: bool,
+                sum: Option<&mut DeviceF64>, max: Option<&mut DeviceF64>) {
+        let (kind, xs) = scale_args(s);
+        let n_out = sum.as_ref().map(|v| v.n).or(max.as_ref().map(|v| v.n)).unwrap_or(0);
+        check(unsafe { aeth_chan_exec_sums(self.h, hist.map_or(ptr::null(), |h| h.p as *const cf32), x.p, x.n, first_frame, AETH_SIGN_REF_FWD,
+                                           kind, xs, mirror as i32, block, if general { AETH_SUMS_GENERAL } else { 0 },
+                                           sum.map_or(ptr::null_mut(), |v| v.p), max.map_or(ptr::null_mut(), |v| v.p), n_out) });
     }
 }
 impl<'c> Drop for Channelizer<'c> { fn drop(&mut self) { unsafe { aeth_chan_destroy(self.h); } } }
