@@ -36,6 +36,8 @@ from . import sync                                        # noqa: E402
 from . import mov                                         # noqa: E402
 from . import cc                                          # noqa: E402
 from .cc import ConvCode                                  # noqa: E402
+from . import remap                                       # noqa: E402
+from .remap import Remap                                  # noqa: E402
 from . import ofdm                                        # noqa: E402
 from .ofdm import Ofdm                                    # noqa: E402
 from .modulation import DeviceBits, DeviceSoft            # noqa: E402
@@ -48,5 +50,5 @@ __all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "DeviceF32",
            "LEVEL_DB", "LEVEL_POWER_DB", "Scale", "HipFft",
            "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "Corr", "CorrPeak", "sampling", "modulation", "noise", "sequence", "Sequence",
            "lte_gold", "chan", "Channelizer", "synth", "Synthesizer", "resamp", "Resampler", "arb", "ArbResampler", "step_word",
-           "nco", "Nco", "sync", "mov", "cc", "ConvCode", "ofdm", "Ofdm", "DeviceBits", "DeviceSoft",
+           "nco", "Nco", "sync", "mov", "cc", "ConvCode", "remap", "Remap", "ofdm", "Ofdm", "DeviceBits", "DeviceSoft",
            "assert_evm", "evm_db"]

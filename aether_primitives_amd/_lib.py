@@ -261,6 +261,19 @@ PROTOTYPES = {
     "aeth_cc_history": (sz, [vp]),
     "aeth_cc_encode": (i32, [vp, vp, vp, sz, vp, sz]),
     "aeth_cc_decode": (i32, [vp, vp, vp, sz, vp, sz]),
+    "aeth_remap_create": (i32, [vp, vp, sz, sz, pvp]),
+    "aeth_remap_destroy": (i32, [vp]),
+    "aeth_remap_in_period": (sz, [vp]),
+    "aeth_remap_out_period": (sz, [vp]),
+    "aeth_remap_in_count": (sz, [vp, sz]),
+    "aeth_remap_route": (i32, [vp]),
+    "aeth_remap_tile": (sz, [vp]),
+    "aeth_remap_exec": (i32, [vp, vp, sz, vp, sz, C.c_uint8]),
+    "aeth_remap_puncture": (i32, [vp, sz, vp, sz, psz]),
+    "aeth_remap_invert": (i32, [vp, sz, sz, vp]),
+    "aeth_remap_compose": (i32, [vp, sz, sz, vp, sz, sz, vp, sz, psz, psz]),
+    "aeth_remap_rows_cols": (i32, [sz, sz, vp]),
+    "aeth_remap_bicm16": (i32, [sz, sz, vp]),
 }
 
 _lib = None

@@ -55,6 +55,7 @@ typedef struct aeth_synth aeth_synth;   /* polyphase synthesis filter bank: weig
 typedef struct aeth_resamp aeth_resamp; /* polyphase rational resampler: up U, real FIR, down Q in one pass */
 typedef struct aeth_arb aeth_arb;       /* arbitrary-ratio resampler: interpolated polyphase taps behind a Q32.32 time word */
 typedef struct aeth_cc aeth_cc;         /* convolutional code: encoder and block-wise soft-decision Viterbi decoder */
+typedef struct aeth_remap aeth_remap;   /* rate matching: a periodic byte map (puncture, depuncture, interleave, chains) */
 typedef struct aeth_ofdm aeth_ofdm;     /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
@@ -1023,7 +1024,7 @@ AETH_API int aeth_mov_search(aeth_ctx *ctx, int kind, size_t window, size_t lag,
  * each call gets the last k - 1 bits of the one before as its history.
  *
  * The decoder.  Soft values are int8_t, one per coded bit in the encoder's output order; positive means bit 0 is
- * likelier, 0 is an erasure (a depunctured stream simply carries zeros).  A call has N = nbits steps; its history is
+ * likelier, 0 is an erasure (a stream depunctured by aeth_remap_exec carries zeros).  A call has N = nbits steps; its history is
  * A + T steps of n values each before step 0, NULL meaning erasures.
  *   Delay.    out[o] is the decision for step o - T: the decoder is a causal system with delay T.
  *   Blocks.   Output block b is o in [b D, min(N, (b + 1) D)).  Its window is steps [b D - T - A, min(N, (b + 1) D)).
@@ -1059,6 +1060,68 @@ AETH_API int aeth_cc_encode(aeth_cc *cc, const uint8_t *hist_bits_dev, const uin
                             size_t ncoded);
 AETH_API int aeth_cc_decode(aeth_cc *cc, const int8_t *hist_soft_dev, const int8_t *soft_dev, size_t nsoft, uint8_t *bits_dev,
                             size_t nbits);
+
+/* ---- rate matching: periodic byte maps for puncturing and interleaving (no body in the reference) ---- */
+/* What stands between the coder and the mapper of a coded link, and its inverse between aeth_demod_soft and
+ * aeth_cc_decode: puncturing (rate 2/3 and 3/4 from the K = 7 rate 1/2 code), depuncturing to erasures, a block
+ * interleaver, or any chain of them.  All are one operation, a periodic gather of bytes with a constant where nothing is
+ * gathered.
+ *
+ * An aeth_remap holds an input period R_in, an output period R_out and a table map[R_out] of int32_t, each entry -1 or an
+ * index in [0, R_in).  Elements are bytes that the kernel never interprets: the same call moves uint8_t bits and int8_t
+ * soft values.
+ *     out[q R_out + i] = map[i] < 0 ? fill : in[q R_in + map[i]]          q = 0, 1, ...;  0 <= i < R_out
+ * `fill` is a byte argument of the exec call (0: erasures in front of the decoder).  An input index may appear any
+ * number of times (repetition) or not at all (puncturing).
+ *
+ * A call writes n_out bytes: Q = n_out div R_out whole periods, then a partial last period of n_out mod R_out outputs.  It
+ * reads only inside the first aeth_remap_in_count(rm, n_out) input bytes: Q R_in, plus one more than the largest
+ * non-negative map[i] with i < n_out mod R_out (plus 0 when there is none).  n_in below that count is AETH_E_LEN, the
+ * message naming both numbers; a larger n_in is allowed.  A period needs nothing from its neighbours, so the chunks of a
+ * stream cut at any multiple of R_out outputs and R_in inputs concatenate byte for byte with no history.
+ *
+ * Limits, all checked before any device work, the offending value in the message: 1 <= R_in, R_out <= 2^20 and table
+ * entries in [-1, R_in) (the position and the value are named), else AETH_E_ARG; n_in or n_out at or above 2^32 is
+ * AETH_E_UNSUPPORTED (the caller cuts at a period, which costs nothing); an output range that shares a byte with the input
+ * range is AETH_E_ARG.  Pointers may have any byte alignment; n_out = 0 launches nothing.  The object owns the device copy
+ * of its table (uint16_t offsets of a whole tile on the tile route, the int32_t table on the gather route);
+ * aeth_remap_destroy frees it, and a refused create leaves the device's free memory unchanged.
+ *
+ * aeth_remap_route says which kernel a call takes: AETH_REMAP_ROUTE_TILE when a tile of g = aeth_remap_tile(rm) >= 1 whole
+ * periods and its table fit 32 KiB of LDS (the inputs are staged there and every lane assembles 16 output bytes), else
+ * AETH_REMAP_ROUTE_GATHER (table and inputs from global memory; aeth_remap_tile is 0).  The results do not depend on it.
+ *
+ * Not built: elements wider than a byte (cf32 symbol interleavers, pilot insertion), maps that reach into earlier periods
+ * (Forney / convolutional interleavers), bit-packed streams, an aeth_stream_op kind, host-slice flavours. */
+#define AETH_REMAP_ROUTE_TILE 1
+#define AETH_REMAP_ROUTE_GATHER 2
+AETH_API int aeth_remap_create(aeth_ctx *ctx, const int32_t *map, size_t r_out, size_t r_in, aeth_remap **out);
+AETH_API int aeth_remap_destroy(aeth_remap *rm);
+AETH_API size_t aeth_remap_in_period(const aeth_remap *rm);
+AETH_API size_t aeth_remap_out_period(const aeth_remap *rm);
+AETH_API size_t aeth_remap_in_count(const aeth_remap *rm, size_t n_out);
+AETH_API int aeth_remap_route(const aeth_remap *rm);
+AETH_API size_t aeth_remap_tile(const aeth_remap *rm);
+AETH_API int aeth_remap_exec(aeth_remap *rm, const void *in_dev, size_t n_in, void *out_dev, size_t n_out, uint8_t fill);
+/* Host-only table builders: pure integer arithmetic, no context.  Each writes into caller memory; where it takes a
+ * capacity, too small a one is AETH_E_LEN with the needed size in the message.
+ *   puncture   keep[i] & 1 says whether coded bit i of a period of p is sent: R_in = p, R_out = *r_out = the number kept,
+ *              map = the kept positions ascending.  An all-zero keep is AETH_E_ARG.
+ *   invert     inv has r_in entries: inv[j] is the smallest i with map[i] == j, or -1 -- the depuncturer of a puncturer,
+ *              the deinterleaver of an interleaver, the first copy of a repetition.
+ *   compose    b applied to the output of a.  With m = lcm(a_out, b_in): *r_in = a_in m / a_out, *r_out = b_out m / b_in;
+ *              a -1 in either table propagates; a period above 2^20 is AETH_E_UNSUPPORTED.
+ *   rows_cols  written row by row, read column by column: map[c rows + r] = r cols + c (rows cols entries).
+ *   bicm16     the two-step permutation of 802.11a 17.3.5.6 from its formulas: s = max(n_bpsc / 2, 1), coded bit k goes to
+ *              i = (n_cbps / 16) (k mod 16) + k div 16, then to j = s (i div s) + (i + n_cbps - (16 i) div n_cbps) mod s;
+ *              map is the gather form, map[j] = k (n_cbps entries).  n_cbps must be a multiple of 16 s and of n_bpsc,
+ *              else AETH_E_ARG. */
+AETH_API int aeth_remap_puncture(const uint8_t *keep, size_t p, int32_t *map, size_t cap, size_t *r_out);
+AETH_API int aeth_remap_invert(const int32_t *map, size_t r_out, size_t r_in, int32_t *inv);
+AETH_API int aeth_remap_compose(const int32_t *a, size_t a_out, size_t a_in, const int32_t *b, size_t b_out, size_t b_in, int32_t *map,
+                                size_t cap, size_t *r_out, size_t *r_in);
+AETH_API int aeth_remap_rows_cols(size_t rows, size_t cols, int32_t *map);
+AETH_API int aeth_remap_bicm16(size_t n_cbps, size_t n_bpsc, int32_t *map);
 
 /* ---- OFDM symbols (no body in the reference: it has Fft, VecOps::vec_mul and chunks_mut(fft_len) framing only) ---- */
 /* The framing and the one-tap equaliser of an OFDM link; everything else such a link needs is above (aeth_seq_scramble,

@@ -13,6 +13,7 @@
 // aether::Panic carrying the reference's message text.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstddef>
@@ -813,6 +814,80 @@ public:
 
 private:
     aeth_cc *h_ = nullptr;
+};
+
+// ---- rate matching (no body in the reference) --------------------------------------------------------------------------
+// A periodic byte map: out[q r_out + i] = in[q r_in + map[i]], or `fill` where map[i] is -1.  Puncturing, depuncturing to
+// erasures, block interleaving and any chain of them are this one gather.  The table builders are host-only integer
+// arithmetic; device pointers in and out, bytes of any meaning (uint8_t bits, int8_t soft values).
+class Remap {
+public:
+    Remap(Context &ctx, std::vector<int32_t> map, size_t r_in) : ctx_(&ctx), map_(std::move(map)), r_in_(r_in)
+    {
+        check(aeth_remap_create(ctx.get(), map_.data(), map_.size(), r_in_, &h_));
+    }
+    ~Remap() { aeth_remap_destroy(h_); }
+    Remap(const Remap &) = delete;
+    Remap &operator=(const Remap &) = delete;
+    Remap(Remap &&o) noexcept : ctx_(o.ctx_), map_(std::move(o.map_)), r_in_(o.r_in_), h_(o.h_) { o.h_ = nullptr; }
+    // keep[i] & 1: coded bit i of a period of keep.size() is sent
+    static Remap puncture(Context &ctx, const std::vector<uint8_t> &keep)
+    {
+        std::vector<int32_t> map(keep.empty() ? 1 : keep.size());
+        size_t r_out = 0;
+        check(aeth_remap_puncture(keep.data(), keep.size(), map.data(), map.size(), &r_out));
+        map.resize(r_out);
+        return Remap(ctx, std::move(map), keep.size());
+    }
+    // written row by row, read column by column
+    static Remap rows_cols(Context &ctx, size_t rows, size_t cols)
+    {
+        std::vector<int32_t> map(std::min<size_t>(std::max<size_t>(rows * cols, 1), (size_t)1 << 20));
+        check(aeth_remap_rows_cols(rows, cols, map.data()));
+        return Remap(ctx, std::move(map), rows * cols);
+    }
+    // the interleaver of 802.11a 17.3.5.6 over n_cbps coded bits at n_bpsc bits per carrier
+    static Remap bicm16(Context &ctx, size_t n_cbps, size_t n_bpsc)
+    {
+        std::vector<int32_t> map(std::min<size_t>(std::max<size_t>(n_cbps, 1), (size_t)1 << 20));
+        check(aeth_remap_bicm16(n_cbps, n_bpsc, map.data()));
+        return Remap(ctx, std::move(map), n_cbps);
+    }
+    // the depuncturer of a puncturer, the deinterleaver of an interleaver, the first copy of a repetition
+    Remap inverse() const
+    {
+        std::vector<int32_t> inv(r_in_);
+        check(aeth_remap_invert(map_.data(), map_.size(), r_in_, inv.data()));
+        return Remap(*ctx_, std::move(inv), map_.size());
+    }
+    // `other` applied to the output of this map, as one map
+    Remap then(const Remap &other) const
+    {
+        std::vector<int32_t> map((size_t)1 << 20);
+        size_t r_out = 0, r_in = 0;
+        check(aeth_remap_compose(map_.data(), map_.size(), r_in_, other.map_.data(), other.map_.size(), other.r_in_, map.data(), map.size(),
+                                 &r_out, &r_in));
+        map.resize(r_out);
+        return Remap(*ctx_, std::move(map), r_in);
+    }
+    size_t in_period() const { return aeth_remap_in_period(h_); }
+    size_t out_period() const { return aeth_remap_out_period(h_); }
+    // the input bytes a call that writes n_out bytes reads
+    size_t in_count(size_t n_out) const { return aeth_remap_in_count(h_, n_out); }
+    int route() const { return aeth_remap_route(h_); }          // AETH_REMAP_ROUTE_TILE or AETH_REMAP_ROUTE_GATHER
+    size_t tile() const { return aeth_remap_tile(h_); }         // periods per tile; 0 on the gather route
+    void exec(const void *in_dev, size_t n_in, void *out_dev, size_t n_out, uint8_t fill = 0)
+    {
+        check(aeth_remap_exec(h_, in_dev, n_in, out_dev, n_out, fill));
+    }
+    const std::vector<int32_t> &map() const { return map_; }
+    aeth_remap *get() const { return h_; }
+
+private:
+    Context *ctx_;
+    std::vector<int32_t> map_;
+    size_t r_in_;
+    aeth_remap *h_ = nullptr;
 };
 
 // ---- OFDM symbols (no body in the reference: it has Fft, vec_mul and chunks_mut(fft_len) framing only) ----------------

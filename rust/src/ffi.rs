@@ -13,6 +13,8 @@ use std::os::raw::{c_char, c_double, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_resamp { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_arb { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_cc { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_remap { _p: [u8; 0] }
+pub const AETH_REMAP_ROUTE_TILE: c_int = 1; pub const AETH_REMAP_ROUTE_GATHER: c_int = 2;
 #[repr(C)] pub struct aeth_ofdm { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
@@ -325,6 +327,20 @@ extern "C" {
                           ncoded: usize) -> c_int;
     pub fn aeth_cc_decode(cc: *mut aeth_cc, hist_soft_dev: *const i8, soft_dev: *const i8, nsoft: usize, bits_dev: *mut u8,
                           nbits: usize) -> c_int;
+    pub fn aeth_remap_create(ctx: *mut aeth_ctx, map: *const i32, r_out: usize, r_in: usize, out: *mut *mut aeth_remap) -> c_int;
+    pub fn aeth_remap_destroy(rm: *mut aeth_remap) -> c_int;
+    pub fn aeth_remap_in_period(rm: *const aeth_remap) -> usize;
+    pub fn aeth_remap_out_period(rm: *const aeth_remap) -> usize;
+    pub fn aeth_remap_in_count(rm: *const aeth_remap, n_out: usize) -> usize;
+    pub fn aeth_remap_route(rm: *const aeth_remap) -> c_int;
+    pub fn aeth_remap_tile(rm: *const aeth_remap) -> usize;
+    pub fn aeth_remap_exec(rm: *mut aeth_remap, in_dev: *const c_void, n_in: usize, out_dev: *mut c_void, n_out: usize, fill: u8) -> c_int;
+    pub fn aeth_remap_puncture(keep: *const u8, p: usize, map: *mut i32, cap: usize, r_out: *mut usize) -> c_int;
+    pub fn aeth_remap_invert(map: *const i32, r_out: usize, r_in: usize, inv: *mut i32) -> c_int;
+    pub fn aeth_remap_compose(a: *const i32, a_out: usize, a_in: usize, b: *const i32, b_out: usize, b_in: usize, map: *mut i32,
+                              cap: usize, r_out: *mut usize, r_in: *mut usize) -> c_int;
+    pub fn aeth_remap_rows_cols(rows: usize, cols: usize, map: *mut i32) -> c_int;
+    pub fn aeth_remap_bicm16(n_cbps: usize, n_bpsc: usize, map: *mut i32) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;

@@ -569,6 +569,64 @@ impl<'c> ConvCode<'c> {
 }
 impl<'c> Drop for ConvCode<'c> { fn drop(&mut self) { unsafe { aeth_cc_destroy(self.h); } } }
 
+/// Rate matching (no body in the reference): a periodic byte map, out[q r_out + i] = in[q r_in + map[i]], or `fill` where
+/// map[i] is -1.  Puncturing, depuncturing to erasures, block interleaving and any chain of them are this one gather.  The
+/// table builders are host-only integer arithmetic and need no context.
+pub struct Remap<'c> { h: *mut aeth_remap, map: Vec<i32>, r_in: usize, ctx: &'c Context }
+impl<'c> Remap<'c> {
+    pub fn new(ctx: &'c Context, map: &[i32], r_in: usize) -> Remap<'c> {
+        let mut h = ptr::null_mut();
+        check(unsafe { aeth_remap_create(ctx.h, map.as_ptr(), map.len(), r_in, &mut h) });
+        Remap { h, map: map.to_vec(), r_in, ctx }
+    }
+    /// keep[i] & 1: coded bit i of a period of keep.len() is sent
+    pub fn puncture(ctx: &'c Context, keep: &[u8]) -> Remap<'c> {
+        let (mut map, mut r_out) = (vec![0i32; keep.len().max(1)], 0usize);
+        check(unsafe { aeth_remap_puncture(keep.as_ptr(), keep.len(), map.as_mut_ptr(), map.len(), &mut r_out) });
+        map.truncate(r_out);
+        Remap::new(ctx, &map, keep.len())
+    }
+    /// written row by row, read column by column
+    pub fn rows_cols(ctx: &'c Context, rows: usize, cols: usize) -> Remap<'c> {
+        let mut map = vec![0i32; (rows * cols).clamp(1, 1 << 20)];
+        check(unsafe { aeth_remap_rows_cols(rows, cols, map.as_mut_ptr()) });
+        Remap::new(ctx, &map, rows * cols)
+    }
+    /// the interleaver of 802.11a 17.3.5.6 over n_cbps coded bits at n_bpsc bits per carrier
+    pub fn bicm16(ctx: &'c Context, n_cbps: usize, n_bpsc: usize) -> Remap<'c> {
+        let mut map = vec![0i32; n_cbps.clamp(1, 1 << 20)];
+        check(unsafe { aeth_remap_bicm16(n_cbps, n_bpsc, map.as_mut_ptr()) });
+        Remap::new(ctx, &map, n_cbps)
+    }
+    /// the depuncturer of a puncturer, the deinterleaver of an interleaver, the first copy of a repetition
+    pub fn inverse(&self) -> Remap<'c> {
+        let mut inv = vec![0i32; self.r_in];
+        check(unsafe { aeth_remap_invert(self.map.as_ptr(), self.map.len(), self.r_in, inv.as_mut_ptr()) });
+        Remap::new(self.ctx, &inv, self.map.len())
+    }
+    /// `other` applied to the output of this map, as one map
+    pub fn then(&self, other: &Remap<'c>) -> Remap<'c> {
+        let (mut map, mut r_out, mut r_in) = (vec![0i32; 1 << 20], 0usize, 0usize);
+        check(unsafe { aeth_remap_compose(self.map.as_ptr(), self.map.len(), self.r_in, other.map.as_ptr(), other.map.len(), other.r_in,
+                                          map.as_mut_ptr(), map.len(), &mut r_out, &mut r_in) });
+        map.truncate(r_out);
+        Remap::new(self.ctx, &map, r_in)
+    }
+    pub fn in_period(&self) -> usize { unsafe { aeth_remap_in_period(self.h) } }
+    pub fn out_period(&self) -> usize { unsafe { aeth_remap_out_period(self.h) } }
+    /// the input bytes a call that writes `n_out` bytes reads
+    pub fn in_count(&self, n_out: usize) -> usize { unsafe { aeth_remap_in_count(self.h, n_out) } }
+    /// AETH_REMAP_ROUTE_TILE or AETH_REMAP_ROUTE_GATHER
+    pub fn route(&self) -> i32 { unsafe { aeth_remap_route(self.h) } }
+    /// periods per tile on the tile route, 0 on the gather route
+    pub fn tile(&self) -> usize { unsafe { aeth_remap_tile(self.h) } }
+    /// device pointers to bytes of any meaning (u8 bits, i8 soft values); `fill` stands where the map holds -1
+    pub fn exec(&mut self, in_dev: *const c_void, n_in: usize, out_dev: *mut c_void, n_out: usize, fill: u8) {
+        check(unsafe { aeth_remap_exec(self.h, in_dev, n_in, out_dev, n_out, fill) });
+    }
+}
+impl<'c> Drop for Remap<'c> { fn drop(&mut self) { unsafe { aeth_remap_destroy(self.h); } } }
+
 /// OFDM symbols (no body in the reference: it has `Fft`, `vec_mul` and `chunks_mut(fft_len)` framing only): a transform
 /// length, a cyclic prefix and a carrier list (`bins[k]`: the FFT bin of carrier k).  `demod` strips the prefix, transforms
 /// with the sign of `Fft::fwd`, picks the carriers and multiplies by `eq[k]` in one kernel; `modulate` is the way back with
