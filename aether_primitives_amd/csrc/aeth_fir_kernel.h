@@ -80,15 +80,27 @@ constexpr int V_ALL = V_PRIO | V_XOR | V_SPREAD | V_DECIM | V_DEMOD | V_DM_BPSK 
                       V_PEAK;
 
 // cache-policy bits of the streamed accesses (aux operand of the buffer instructions: 1 = sc0, 2 = nt, 16 = sc1):
-// loads nt, stores nt + sc1 (tools/nt_modes.hip: 6.55 against 6.43 TB/s for nt alone)
+// loads nt, stores nt + sc1.  Chosen by an element-wise copy at first (tools/nt_modes.hip), since measured in the kernel
+// itself, 8-byte accesses, persistent workgroups, two launches in flight (tools/fir_lab.hip, profiles/fir_policy_lab.txt;
+// per cent of the launch time against these values): loads plain or sc1 +3.3 ... +3.7, nt + sc1 the same as nt; stores
+// nt alone +0.1 ... +0.5 (one queue: +0.9 ... +1.3), sc1 alone +3.3 ... +6.2, plain +5.2 ... +8.2.
 constexpr int kLoadAux = 2, kStoreAux = 18;
-// ... except a window's halo slots, whose lines a second workgroup (on another XCD) reads within the same round: the
-// last ov samples of a window are the first ov of its right neighbour's.  Plain (0) instead of nt: +3.2 % on the
-// headline with 20 and with 2000 steps, six alternating runs each (profiles/fir_head_bench.txt).  FETCH_SIZE does not
-// move (139.0 MB per launch before and after, profiles/r06_summary.json): it counts what L2 requests, in front of the
-// memory-side cache, so the gain is the second reader's requests being served there, not fewer of them.  sc1 (16) was
-// built, gives the same bits, and was not measured.
+// ... except some slots of a window, which are loaded plain (0) instead of nt.  That began as the window's halo -- the
+// last ov samples of a window are the first ov of its right neighbour's, read by a workgroup on another XCD in the same
+// round -- in slot 0 and slot P-1: +3.2 % on the headline (profiles/fir_head_bench.txt).  The lab says the sharing is not
+// what pays: plain on two slots nobody shares (7 and 8) gains the same, on one of the halo slots half of it, on only the
+// shared HALF of each halo slot (a wave-uniform branch around the load) nothing.  What counts is the share of a window's
+// loads that go without the hint, wherever they sit: 1 / 2 / 3 / 4 / 5 / 6 / 8 / 16 of 16 slots give +1.8 / 0 / -1.5 /
+// -2.0 ... -2.6 / -2.3 ... -2.7 / -1.5 / +3.1 / +3.5 % of the launch time against two (one queue: the same curve, -2.1
+// at four).  sc1 (16) and sc0 (1) on these slots: the same as plain to 0.4 %.
 constexpr int kHaloAux = 0;
+// The slots that take kHaloAux, bit m = slot m: the first and the last, and at N = 2048 with 16 slots (the configuration
+// the table was measured on, as V_XOR) the two at either end: a quarter of the window, and exactly the halo of the longest
+// filters the plan takes (ov = 256).  Frames (ov = 0) go through the same builds with the same slots.
+template <class C> constexpr unsigned plain_slots()
+{
+    return (C::N == 2048 && C::P == 16) ? 0xC003u : (1u | 1u << (C::P - 1));
+}
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -100,16 +112,32 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ cf as_cf(u32x2 v) { return __builtin_bit_cast(cf, v); }
 __device__ __forceinline__ u32x2 as_u32x2(cf v) { return __builtin_bit_cast(u32x2, v); }
 
-// Slot m of a window through its descriptor.  The aux operand is an immediate and ov a run-time value, so "halo slot" is
-// a compile-time rule: the first and the last slot.  The halo is window elements [0, ov) and [hop, N): exact for
-// ov <= T (N = 2048 with up to 129 taps), a partial saving and no error when ov > T (200 taps: ov = 256, slots 1 and 14
-// keep the hint).  Frames (ov = 0) go through the same builds and lose the hint on these two slots as well.
+// What a build of the kernel does with those constants.  Every configuration the library launches takes this primary
+// template, the shipped rule; tools/fir_lab.hip specialises it for configurations of its own (a Cfg with a LabPolicy
+// member) to time other policies, halo rules and burst orders beside it in one process.  The policy hangs on C and not on
+// a template parameter of its own because the mangled names of the library's builds are parsed (see VAR above).
+template <class C, class = void>
+struct StreamPolicy {
+    static constexpr int store = kStoreAux;                 // the 8-byte sample stores of store_block
+    static constexpr int slot(int i) { return i; }          // the i-th load of a window's burst fetches this slot
+    // Slot m of a window through its descriptor.  The aux operand is an immediate, so which slots go without the hint
+    // is a compile-time rule on m (plain_slots): no branch, one load per slot, and the policy is a hint only -- a slot on
+    // either side of the rule returns the same bytes.
+    template <bool NT, class RS>
+    static __device__ __forceinline__ cf load(RS rs, int tid, int m)
+    {
+        const int off = (tid + m * C::T) * 8;
+        if ((plain_slots<C>() >> m) & 1) return as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, NT ? kHaloAux : 0));
+        return as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, NT ? kLoadAux : 0));
+    }
+};
+
+// the i-th load of a window's burst: slot m = StreamPolicy<C>::slot(i) into its register
 template <class C, bool NT, class RS>
-__device__ __forceinline__ cf load_slot(RS rs, int tid, int m)
+__device__ __forceinline__ void load_slot(cf (&x)[C::P], RS rs, int tid, int i)
 {
-    const int off = (tid + m * C::T) * 8;
-    if (m == 0 || m == C::P - 1) return as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, NT ? kHaloAux : 0));
-    return as_cf(__builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, NT ? kLoadAux : 0));
+    const int m = StreamPolicy<C>::slot(i);
+    x[m] = StreamPolicy<C>::template load<NT>(rs, tid, m);
 }
 
 // one block's input window -> registers (slot m = window element tid + m*T)
@@ -129,8 +157,8 @@ __device__ __forceinline__ void load_window(cf (&x)[C::P], const FmiArgs &a, lon
             int bytes = (int)(left < a.frame_n ? left : a.frame_n) * 8;
             auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
-            for (int m = 0; m < C::P; m++)
-                x[m] = load_slot<C, NT>(rs, tid, m);
+            for (int i = 0; i < C::P; i++)
+                load_slot<C, NT>(x, rs, tid, i);
             // (the window's oldest ov-nhist samples are zeroed when the window is consumed: doing it
             // here would put a wait for the load right behind its issue)
             return;
@@ -184,8 +212,8 @@ __device__ __forceinline__ void load_window_srd(cf (&x)[C::P], const FmiArgs &a,
     const int bytes = active ? (int)(left < a.frame_n ? left : a.frame_n) * 8 : 0;
     auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
-    for (int m = 0; m < C::P; m++)
-        x[m] = load_slot<C, NT>(rs, tid, m);
+    for (int i = 0; i < C::P; i++)
+        load_slot<C, NT>(x, rs, tid, i);
 }
 
 // the same, slots [M0, M1) only (V_SPREAD: the window arrives in four instalments)
@@ -198,8 +226,8 @@ __device__ __forceinline__ void load_window_srd_part(cf (&x)[C::P], const FmiArg
     const int bytes = active ? (int)(left < a.frame_n ? left : a.frame_n) * 8 : 0;
     auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf *>(a.in + win0), 0, bytes, 0x00020000);
 #pragma unroll
-    for (int m = M0; m < M1; m++)
-        x[m] = load_slot<C, NT>(rs, tid, m);
+    for (int i = M0; i < M1; i++)
+        load_slot<C, NT>(x, rs, tid, i);
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -385,7 +413,7 @@ __device__ __forceinline__ void store_block(const cf (&w)[C::P], const FmiArgs &
             const bool keep = e >= a.ov && q * a.dec.d == o && (long long)o < a.n;
             const int off = keep ? (int)(q - q0) * 8 : 0x7ffffff0;
             cf v = SCALED ? cscale_k(w[m], ss) : w[m];
-            __builtin_amdgcn_raw_buffer_store_b64(as_u32x2(v), rs, off, 0, NT ? kStoreAux : 0);
+            __builtin_amdgcn_raw_buffer_store_b64(as_u32x2(v), rs, off, 0, NT ? StreamPolicy<C>::store : 0);
         }
     } else if constexpr (C::F == 1) {
         long long left = a.n - base;
@@ -400,7 +428,7 @@ __device__ __forceinline__ void store_block(const cf (&w)[C::P], const FmiArgs &
             const int e = tid + m * C::T;
             const int off = (e >= a.ov) ? e * 8 : 0x7ffffff0;
             cf v = SCALED ? cscale_k(w[m], ss) : w[m];
-            __builtin_amdgcn_raw_buffer_store_b64(as_u32x2(v), rs, off, 0, NT ? kStoreAux : 0);   // nt + sc1: streamed stores (tools/nt_modes.hip: 6.55 vs 6.43 TB/s for nt alone)
+            __builtin_amdgcn_raw_buffer_store_b64(as_u32x2(v), rs, off, 0, NT ? StreamPolicy<C>::store : 0);   // streamed stores (kStoreAux)
         }
     } else {
 #pragma unroll
