@@ -274,6 +274,23 @@ PROTOTYPES = {
     "aeth_remap_compose": (i32, [vp, sz, sz, vp, sz, sz, vp, sz, psz, psz]),
     "aeth_remap_rows_cols": (i32, [sz, sz, vp]),
     "aeth_remap_bicm16": (i32, [sz, sz, vp]),
+    "aeth_crc_create": (i32, [vp, C.c_uint32, u64, u64, u64, pvp]),
+    "aeth_crc_destroy": (i32, [vp]),
+    "aeth_crc_width": (C.c_uint32, [vp]),
+    "aeth_crc_poly": (u64, [vp]),
+    "aeth_crc_init": (u64, [vp]),
+    "aeth_crc_xorout": (u64, [vp]),
+    "aeth_crc_residue": (u64, [vp]),
+    "aeth_crc_route": (i32, [vp, sz, sz]),
+    "aeth_crc_route_frame_bits": (sz, [vp]),
+    "aeth_crc_frames_per_workgroup": (sz, [vp, sz]),
+    "aeth_crc_named": (i32, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+    "aeth_crc_host": (i32, [C.c_uint32, u64, u64, u64, vp, sz, C.POINTER(u64)]),
+    "aeth_crc_exec": (i32, [vp, vp, sz, sz, vp, vp]),
+    "aeth_crc_attach": (i32, [vp, vp, sz, sz, vp]),
+    "aeth_crc_check": (i32, [vp, vp, sz, sz, u64, vp, vp, vp]),
+    "aeth_bits_pack": (i32, [vp, vp, sz, i32, vp, sz]),
+    "aeth_bits_unpack": (i32, [vp, vp, sz, i32, vp, sz]),
 }
 
 _lib = None

@@ -124,9 +124,9 @@ struct HostIO {
 };
 
 // Tuning knobs: environment integers that are consulted ONLY when the process was started with AETH_TUNING=1; a
-// normal run never reads them.  libaether_hip.so carries the eight that choose between SHIPPED behaviours, all
+// normal run never reads them.  libaether_hip.so carries the nine that choose between SHIPPED behaviours, all
 // documented in include/aether_hip.h ("Tuning knobs"): AETH_FIR_GRID_FIRST, AETH_FIR_GRID_CHAINED, AETH_FIR_SPREAD,
-// AETH_NT, AETH_PIPE_THREADS, AETH_PIPE_MIXED, AETH_SYNC_SPIN_US, AETH_SPEC_SLICE_KIB.
+// AETH_NT, AETH_PIPE_THREADS, AETH_PIPE_MIXED, AETH_SYNC_SPIN_US, AETH_SPEC_SLICE_KIB, AETH_CRC_ROUTE.
 int tuning_int(const char *name, int dflt);
 // Lab knobs (tools/tune_*.py, prime_route.py, vs_rocfft.py sweeps): routes and shapes that were measured and not
 // kept.  They exist only in the lab build (`make LAB=1` -> lib/libaether_hip_lab.so, -DAETH_LAB=1); in the product

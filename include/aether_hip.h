@@ -56,6 +56,7 @@ typedef struct aeth_resamp aeth_resamp; /* polyphase rational resampler: up U, r
 typedef struct aeth_arb aeth_arb;       /* arbitrary-ratio resampler: interpolated polyphase taps behind a Q32.32 time word */
 typedef struct aeth_cc aeth_cc;         /* convolutional code: encoder and block-wise soft-decision Viterbi decoder */
 typedef struct aeth_remap aeth_remap;   /* rate matching: a periodic byte map (puncture, depuncture, interleave, chains) */
+typedef struct aeth_crc aeth_crc;       /* frame checks: a CRC of width 1 .. 64 over bit frames: registers, attach, check */
 typedef struct aeth_ofdm aeth_ofdm;     /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
@@ -98,7 +99,9 @@ enum { AETH_SIGN_REF_FWD = +1, AETH_SIGN_REF_BWD = -1 };
  *                          (default 0: both sides staged -- the mixed form measured 2.4 x slower downloads)
  *   AETH_SYNC_SPIN_US      how long aeth_ctx_sync polls both queues before it blocks (default 2000)
  *   AETH_SPEC_SLICE_KIB    KiB of spectrum the general route of aeth_chan_exec_sums keeps at a time (default 65536; the
- *                          result does not depend on it) */
+ *                          result does not depend on it)
+ *   AETH_CRC_ROUTE         2: aeth_crc_exec / attach / check take the long route for every L >= 1 (default 0: by L,
+ *                          aeth_crc_route; the result does not depend on it) */
 AETH_API const char *aeth_last_error(void);
 AETH_API int aeth_version(void);                     /* 0x00MMmmpp */
 AETH_API int aeth_device_count(int *count);
@@ -1092,7 +1095,7 @@ AETH_API int aeth_cc_decode(aeth_cc *cc, const int8_t *hist_soft_dev, const int8
  * AETH_REMAP_ROUTE_GATHER (table and inputs from global memory; aeth_remap_tile is 0).  The results do not depend on it.
  *
  * Not built: elements wider than a byte (cf32 symbol interleavers, pilot insertion), maps that reach into earlier periods
- * (Forney / convolutional interleavers), bit-packed streams, an aeth_stream_op kind, host-slice flavours. */
+ * (Forney / convolutional interleavers), maps over bit-packed streams (aeth_bits_unpack first), an aeth_stream_op kind, host-slice flavours. */
 #define AETH_REMAP_ROUTE_TILE 1
 #define AETH_REMAP_ROUTE_GATHER 2
 AETH_API int aeth_remap_create(aeth_ctx *ctx, const int32_t *map, size_t r_out, size_t r_in, aeth_remap **out);
@@ -1122,6 +1125,85 @@ AETH_API int aeth_remap_compose(const int32_t *a, size_t a_out, size_t a_in, con
                                 size_t cap, size_t *r_out, size_t *r_in);
 AETH_API int aeth_remap_rows_cols(size_t rows, size_t cols, int32_t *map);
 AETH_API int aeth_remap_bicm16(size_t n_cbps, size_t n_bpsc, int32_t *map);
+
+/* ---- frame checks: CRC attach and check over bit frames, bit packing (no body in the reference) ---- */
+/* The last step of every frame format: the 802.11 FCS, CRC-24A/B on LTE transport and code blocks, the RNTI-masked
+ * CRC-16 of a control channel.  Everything is integer arithmetic and defined byte for byte.
+ *
+ * An aeth_crc object holds a width r with 1 <= r <= 64.  It holds poly, the low r coefficients of the generator; x^r is
+ * implied and bit 0 must be set.  It holds init and xorout, both below 2^r.
+ *
+ * A message is a run of bytes, one per bit.  Only the lowest bit of each byte counts, as in aeth_seq_scramble.  Per
+ * message bit b, in stream order:
+ *     fb  = ((reg >> (r-1)) & 1) ^ b
+ *     reg = (reg << 1) & (2^r - 1);   if fb: reg ^= poly
+ * The register of a frame is reg after its last bit, starting from init.  The check value is reg ^ xorout.  The check
+ * bits are c[j] = (value >> (r-1-j)) & 1 for j = 0 .. r-1, highest coefficient first.  That is the transmission order of
+ * 802.11 and 3GPP.  "Reflected" catalogue entries are this definition applied to bytes unpacked LSB first.
+ *
+ * aeth_crc_named (host only) fills the parameters of a catalogue name; an unknown name is AETH_E_ARG and the message
+ * lists the known ones: crc-8, crc-8/lte, crc-16/xmodem (the LTE CRC-16), crc-16/ibm-3740, crc-16/genibus, crc-24/lte-a,
+ * crc-24/lte-b, crc-32/bzip2, crc-64/ecma-182, and crc-32 (802.3, the 802.11 FCS): the parameters of crc-32/bzip2, for a
+ * caller that unpacks bytes LSB first (aeth_bits_unpack with AETH_BITS_LSB_FIRST); the 32 check bits packed LSB first
+ * are then the four bytes of the usual CRC-32, lowest first.
+ * aeth_crc_residue is host arithmetic: the register (before xorout) that any frame followed by its own check bits leaves
+ * (0xC704DD7B for crc-32).  aeth_crc_host runs the definition on host memory with no context; *reg is the register.
+ *
+ * aeth_crc_exec, the streaming primitive: F frames of L bits, contiguous.  state_out[f] (uint64_t) is the register of
+ * frame f started from state_in[f], or from init when state_in_dev is NULL; xorout is not applied.  A frame cut at any
+ * bit, the first call's state_out given as the second call's state_in, gives the bytes of one call.  L = 0 returns the
+ * start state.
+ * aeth_crc_attach: the output is F frames of L + r bytes, each the message with every byte reduced to & 1, followed by
+ * the check bits.
+ * aeth_crc_check: the input is F frames of L + r bytes.  Per frame, diff[f] = (received check bits read as a word, first
+ * bit highest) ^ (check value of the L message bits) ^ mask; mask is below 2^r, 0 for a plain check or an RNTI-style
+ * scrambling word.  A frame is good when diff == 0; mask = 0 on a masked frame returns the mask in diff.  payload_dev
+ * (F L bytes, & 1) and diff_dev are optional; summary_dev receives {n_bad, first_bad}, first_bad = F when no frame is
+ * bad, made by a fold of per-workgroup records and so the same in every run.  At least one of the three must be non-NULL.
+ * aeth_bits_pack takes & 1 of every byte and needs nbytes == ceil(nbits / 8); bit i goes to byte i div 8, at bit i mod 8
+ * (AETH_BITS_LSB_FIRST) or 7 - i mod 8 (AETH_BITS_MSB_FIRST); the unused bits of the last byte are 0.  aeth_bits_unpack
+ * needs nbits <= 8 nbytes and writes 0 / 1.
+ *
+ * All device calls are ordered on the context's stream and none waits.  Everything is validated before any device work,
+ * the offending value in the message: null handles or pointers, r outside 1 .. 64, an even poly, poly, init, xorout or
+ * mask at or above 2^r, an unknown order AETH_E_ARG; a wrong nbytes or nbits AETH_E_LEN; a call whose input or output
+ * reaches 2^32 bytes AETH_E_UNSUPPORTED (the caller cuts and carries the state); an output range that shares a byte with
+ * an input range (or another output) AETH_E_ARG.  Pointers to bits and bytes may have any byte alignment; the uint64_t
+ * arrays and the summary are 8-byte aligned (AETH_E_ALIGN).  F = 0 launches nothing, except
+ * that check still writes the summary {0, 0}.  aeth_crc_destroy(NULL) is AETH_OK and getters on NULL return 0.
+ *
+ * Routes.  aeth_crc_route(crc, L, F) is AETH_CRC_ROUTE_FRAMES for L <= aeth_crc_route_frame_bits(crc) (16384): a group of
+ * 4 .. 64 lanes owns a frame, aeth_crc_frames_per_workgroup(crc, frame bytes) frames share a workgroup, and attach and
+ * check store from the kernel that forms the registers.  Longer frames take AETH_CRC_ROUTE_LONG: chunks of 16384 bits
+ * over many workgroups, their registers in a scratch the object owns (freed by aeth_crc_destroy), a second launch that
+ * combines them, and a third that stores for attach and check.  The results never depend on the route.  The object also
+ * owns its weight table (129 KiB of device memory).
+ *
+ * Not built: frames of differing length in one call, strided frames, soft-value input, an aeth_stream_op kind, host-slice
+ * flavours, generator polynomials above degree 64. */
+#define AETH_CRC_ROUTE_FRAMES 1
+#define AETH_CRC_ROUTE_LONG 2
+#define AETH_BITS_LSB_FIRST 0
+#define AETH_BITS_MSB_FIRST 1
+typedef struct aeth_crc_summary { uint64_t n_bad; uint64_t first_bad; } aeth_crc_summary;
+AETH_API int aeth_crc_create(aeth_ctx *ctx, uint32_t r, uint64_t poly, uint64_t init, uint64_t xorout, aeth_crc **out);
+AETH_API int aeth_crc_destroy(aeth_crc *crc);
+AETH_API uint32_t aeth_crc_width(const aeth_crc *crc);
+AETH_API uint64_t aeth_crc_poly(const aeth_crc *crc);
+AETH_API uint64_t aeth_crc_init(const aeth_crc *crc);
+AETH_API uint64_t aeth_crc_xorout(const aeth_crc *crc);
+AETH_API uint64_t aeth_crc_residue(const aeth_crc *crc);
+AETH_API int aeth_crc_route(const aeth_crc *crc, size_t L, size_t F);
+AETH_API size_t aeth_crc_route_frame_bits(const aeth_crc *crc);
+AETH_API size_t aeth_crc_frames_per_workgroup(const aeth_crc *crc, size_t frame_bytes);
+AETH_API int aeth_crc_named(const char *name, uint32_t *r, uint64_t *poly, uint64_t *init, uint64_t *xorout);
+AETH_API int aeth_crc_host(uint32_t r, uint64_t poly, uint64_t init, uint64_t xorout, const uint8_t *bits_host, size_t L, uint64_t *reg);
+AETH_API int aeth_crc_exec(aeth_crc *crc, const uint8_t *bits_dev, size_t L, size_t F, const uint64_t *state_in_dev, uint64_t *state_out_dev);
+AETH_API int aeth_crc_attach(aeth_crc *crc, const uint8_t *in_dev, size_t L, size_t F, uint8_t *out_dev);
+AETH_API int aeth_crc_check(aeth_crc *crc, const uint8_t *in_dev, size_t L, size_t F, uint64_t mask, uint64_t *diff_dev, uint8_t *payload_dev,
+                            aeth_crc_summary *summary_dev);
+AETH_API int aeth_bits_pack(aeth_ctx *ctx, const uint8_t *bits_dev, size_t nbits, int order, uint8_t *bytes_dev, size_t nbytes);
+AETH_API int aeth_bits_unpack(aeth_ctx *ctx, const uint8_t *bytes_dev, size_t nbytes, int order, uint8_t *bits_dev, size_t nbits);
 
 /* ---- OFDM symbols (no body in the reference: it has Fft, VecOps::vec_mul and chunks_mut(fft_len) framing only) ---- */
 /* The framing and the one-tap equaliser of an OFDM link; everything else such a link needs is above (aeth_seq_scramble,

@@ -890,6 +890,74 @@ private:
     aeth_remap *h_ = nullptr;
 };
 
+// ---- frame checks: CRC attach and check over bit frames, bit packing (no body in the reference) ----------------------
+// A CRC of width r <= 64: poly holds the generator's low r coefficients, bits are one byte per bit, first bit first, and
+// the check bits go out highest coefficient first.  Frames are contiguous and of one length.  registers is the streaming
+// primitive (no xorout; a frame cut anywhere continues from the states of the call before), attach appends the r check
+// bits, check forms diff = received ^ computed ^ mask per frame, strips the payload and folds {n_bad, first_bad}.  Device
+// pointers in and out, ordered on the context's stream.
+class Crc {
+public:
+    Crc(Context &ctx, uint32_t r, uint64_t poly, uint64_t init = 0, uint64_t xorout = 0)
+    {
+        check(aeth_crc_create(ctx.get(), r, poly, init, xorout, &h_));
+    }
+    // a catalogue name: "crc-24/lte-a", "crc-32", ... (aeth_crc_named)
+    static Crc named(Context &ctx, const char *name)
+    {
+        uint32_t r = 0;
+        uint64_t poly = 0, init = 0, xorout = 0;
+        check(aeth_crc_named(name, &r, &poly, &init, &xorout));
+        return Crc(ctx, r, poly, init, xorout);
+    }
+    ~Crc() { aeth_crc_destroy(h_); }
+    Crc(const Crc &) = delete;
+    Crc &operator=(const Crc &) = delete;
+    Crc(Crc &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    uint32_t width() const { return aeth_crc_width(h_); }
+    uint64_t poly() const { return aeth_crc_poly(h_); }
+    uint64_t init() const { return aeth_crc_init(h_); }
+    uint64_t xorout() const { return aeth_crc_xorout(h_); }
+    // the register (before xorout) any frame followed by its own check bits leaves
+    uint64_t residue() const { return aeth_crc_residue(h_); }
+    int route(size_t L, size_t F = 1) const { return aeth_crc_route(h_, L, F); }       // AETH_CRC_ROUTE_FRAMES or AETH_CRC_ROUTE_LONG
+    size_t route_frame_bits() const { return aeth_crc_route_frame_bits(h_); }
+    size_t frames_per_workgroup(size_t frame_bytes) const { return aeth_crc_frames_per_workgroup(h_, frame_bytes); }
+    // state_in_dev may be null: every frame starts from init
+    void registers(const uint8_t *bits_dev, size_t L, size_t F, const uint64_t *state_in_dev, uint64_t *state_out_dev)
+    {
+        check(aeth_crc_exec(h_, bits_dev, L, F, state_in_dev, state_out_dev));
+    }
+    void attach(const uint8_t *in_dev, size_t L, size_t F, uint8_t *out_dev) { check(aeth_crc_attach(h_, in_dev, L, F, out_dev)); }
+    // any of the three outputs may be null, not all
+    void check_frames(const uint8_t *in_dev, size_t L, size_t F, uint64_t mask, uint64_t *diff_dev, uint8_t *payload_dev,
+                      aeth_crc_summary *summary_dev)
+    {
+        check(aeth_crc_check(h_, in_dev, L, F, mask, diff_dev, payload_dev, summary_dev));
+    }
+    // the definition on host memory, no context: the register of L bits started from init
+    static uint64_t host(uint32_t r, uint64_t poly, uint64_t init, uint64_t xorout, const uint8_t *bits, size_t L)
+    {
+        uint64_t reg = 0;
+        check(aeth_crc_host(r, poly, init, xorout, bits, L, &reg));
+        return reg;
+    }
+    aeth_crc *get() const { return h_; }
+
+private:
+    aeth_crc *h_ = nullptr;
+};
+
+// one byte per bit <-> eight bits per byte; order is AETH_BITS_LSB_FIRST or AETH_BITS_MSB_FIRST
+inline void pack_bits(Context &ctx, const uint8_t *bits_dev, size_t nbits, int order, uint8_t *bytes_dev)
+{
+    check(aeth_bits_pack(ctx.get(), bits_dev, nbits, order, bytes_dev, (nbits + 7) / 8));
+}
+inline void unpack_bits(Context &ctx, const uint8_t *bytes_dev, size_t nbytes, int order, uint8_t *bits_dev, size_t nbits)
+{
+    check(aeth_bits_unpack(ctx.get(), bytes_dev, nbytes, order, bits_dev, nbits));
+}
+
 // ---- OFDM symbols (no body in the reference: it has Fft, vec_mul and chunks_mut(fft_len) framing only) ----------------
 // A transform length, a cyclic prefix and a carrier list (bins[k]: the FFT bin of carrier k).  demod strips the prefix,
 // transforms with the sign of Fft::fwd, picks the carriers and multiplies by eq[k] in one kernel; mod is the way back with

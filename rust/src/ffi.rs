@@ -15,6 +15,10 @@ use std::os::raw::{c_char, c_double, c_float, c_int, c_uint, c_void};
 #[repr(C)] pub struct aeth_cc { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_remap { _p: [u8; 0] }
 pub const AETH_REMAP_ROUTE_TILE: c_int = 1; pub const AETH_REMAP_ROUTE_GATHER: c_int = 2;
+#[repr(C)] pub struct aeth_crc { _p: [u8; 0] }
+pub const AETH_CRC_ROUTE_FRAMES: c_int = 1; pub const AETH_CRC_ROUTE_LONG: c_int = 2;
+pub const AETH_BITS_LSB_FIRST: c_int = 0; pub const AETH_BITS_MSB_FIRST: c_int = 1;
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_crc_summary { pub n_bad: u64, pub first_bad: u64 }
 #[repr(C)] pub struct aeth_ofdm { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
@@ -341,6 +345,25 @@ extern "C" {
                               cap: usize, r_out: *mut usize, r_in: *mut usize) -> c_int;
     pub fn aeth_remap_rows_cols(rows: usize, cols: usize, map: *mut i32) -> c_int;
     pub fn aeth_remap_bicm16(n_cbps: usize, n_bpsc: usize, map: *mut i32) -> c_int;
+    pub fn aeth_crc_create(ctx: *mut aeth_ctx, r: u32, poly: u64, init: u64, xorout: u64, out: *mut *mut aeth_crc) -> c_int;
+    pub fn aeth_crc_destroy(crc: *mut aeth_crc) -> c_int;
+    pub fn aeth_crc_width(crc: *const aeth_crc) -> u32;
+    pub fn aeth_crc_poly(crc: *const aeth_crc) -> u64;
+    pub fn aeth_crc_init(crc: *const aeth_crc) -> u64;
+    pub fn aeth_crc_xorout(crc: *const aeth_crc) -> u64;
+    pub fn aeth_crc_residue(crc: *const aeth_crc) -> u64;
+    pub fn aeth_crc_route(crc: *const aeth_crc, l: usize, f: usize) -> c_int;
+    pub fn aeth_crc_route_frame_bits(crc: *const aeth_crc) -> usize;
+    pub fn aeth_crc_frames_per_workgroup(crc: *const aeth_crc, frame_bytes: usize) -> usize;
+    pub fn aeth_crc_named(name: *const c_char, r: *mut u32, poly: *mut u64, init: *mut u64, xorout: *mut u64) -> c_int;
+    pub fn aeth_crc_host(r: u32, poly: u64, init: u64, xorout: u64, bits_host: *const u8, l: usize, reg: *mut u64) -> c_int;
+    pub fn aeth_crc_exec(crc: *mut aeth_crc, bits_dev: *const u8, l: usize, f: usize, state_in_dev: *const u64,
+                         state_out_dev: *mut u64) -> c_int;
+    pub fn aeth_crc_attach(crc: *mut aeth_crc, in_dev: *const u8, l: usize, f: usize, out_dev: *mut u8) -> c_int;
+    pub fn aeth_crc_check(crc: *mut aeth_crc, in_dev: *const u8, l: usize, f: usize, mask: u64, diff_dev: *mut u64,
+                          payload_dev: *mut u8, summary_dev: *mut aeth_crc_summary) -> c_int;
+    pub fn aeth_bits_pack(ctx: *mut aeth_ctx, bits_dev: *const u8, nbits: usize, order: c_int, bytes_dev: *mut u8, nbytes: usize) -> c_int;
+    pub fn aeth_bits_unpack(ctx: *mut aeth_ctx, bytes_dev: *const u8, nbytes: usize, order: c_int, bits_dev: *mut u8, nbits: usize) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;

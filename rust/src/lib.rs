@@ -627,6 +627,63 @@ impl<'c> Remap<'c> {
 }
 impl<'c> Drop for Remap<'c> { fn drop(&mut self) { unsafe { aeth_remap_destroy(self.h); } } }
 
+/// Frame checks (no body in the reference): a CRC of width r <= 64 over contiguous frames of one length, bits one byte per
+/// bit, check bits highest coefficient first.  `registers` is the streaming primitive (no xorout), `attach` appends the r
+/// check bits, `check` forms diff = received ^ computed ^ mask per frame, strips the payload and folds {n_bad, first_bad}.
+pub struct Crc<'c> { h: *mut aeth_crc, _ctx: &'c Context }
+impl<'c> Crc<'c> {
+    pub fn new(ctx: &'c Context, r: u32, poly: u64, init: u64, xorout: u64) -> Crc<'c> {
+        let mut h = ptr::null_mut();
+        check(unsafe { aeth_crc_create(ctx.h, r, poly, init, xorout, &mut h) });
+        Crc { h, _ctx: ctx }
+    }
+    /// a catalogue name: "crc-24/lte-a", "crc-32", ...
+    pub fn named(ctx: &'c Context, name: &str) -> Crc<'c> {
+        let (mut r, mut poly, mut init, mut xorout) = (0u32, 0u64, 0u64, 0u64);
+        let name = std::ffi::CString::new(name).expect("a CRC name holds no NUL");
+        check(unsafe { aeth_crc_named(name.as_ptr(), &mut r, &mut poly, &mut init, &mut xorout) });
+        Crc::new(ctx, r, poly, init, xorout)
+    }
+    pub fn width(&self) -> u32 { unsafe { aeth_crc_width(self.h) } }
+    pub fn poly(&self) -> u64 { unsafe { aeth_crc_poly(self.h) } }
+    pub fn init(&self) -> u64 { unsafe { aeth_crc_init(self.h) } }
+    pub fn xorout(&self) -> u64 { unsafe { aeth_crc_xorout(self.h) } }
+    /// the register (before xorout) any frame followed by its own check bits leaves
+    pub fn residue(&self) -> u64 { unsafe { aeth_crc_residue(self.h) } }
+    /// AETH_CRC_ROUTE_FRAMES or AETH_CRC_ROUTE_LONG
+    pub fn route(&self, l: usize, f: usize) -> i32 { unsafe { aeth_crc_route(self.h, l, f) } }
+    pub fn route_frame_bits(&self) -> usize { unsafe { aeth_crc_route_frame_bits(self.h) } }
+    pub fn frames_per_workgroup(&self, frame_bytes: usize) -> usize { unsafe { aeth_crc_frames_per_workgroup(self.h, frame_bytes) } }
+    /// `state_in_dev` may be null: every frame starts from init
+    pub fn registers(&mut self, bits_dev: *const u8, l: usize, f: usize, state_in_dev: *const u64, state_out_dev: *mut u64) {
+        check(unsafe { aeth_crc_exec(self.h, bits_dev, l, f, state_in_dev, state_out_dev) });
+    }
+    pub fn attach(&mut self, in_dev: *const u8, l: usize, f: usize, out_dev: *mut u8) {
+        check(unsafe { aeth_crc_attach(self.h, in_dev, l, f, out_dev) });
+    }
+    /// any of the three outputs may be null, not all
+    pub fn check(&mut self, in_dev: *const u8, l: usize, f: usize, mask: u64, diff_dev: *mut u64, payload_dev: *mut u8,
+                 summary_dev: *mut aeth_crc_summary) {
+        check(unsafe { aeth_crc_check(self.h, in_dev, l, f, mask, diff_dev, payload_dev, summary_dev) });
+    }
+    /// the definition on host memory, no context: the register of `bits` (one byte per bit) started from init
+    pub fn host(r: u32, poly: u64, init: u64, xorout: u64, bits: &[u8]) -> u64 {
+        let mut reg = 0u64;
+        check(unsafe { aeth_crc_host(r, poly, init, xorout, bits.as_ptr(), bits.len(), &mut reg) });
+        reg
+    }
+}
+impl<'c> Drop for Crc<'c> { fn drop(&mut self) { unsafe { aeth_crc_destroy(self.h); } } }
+
+/// one byte per bit -> ceil(nbits / 8) bytes; `order` is AETH_BITS_LSB_FIRST or AETH_BITS_MSB_FIRST
+pub fn pack(ctx: &Context, bits_dev: *const u8, nbits: usize, order: i32, bytes_dev: *mut u8) {
+    check(unsafe { aeth_bits_pack(ctx.h, bits_dev, nbits, order, bytes_dev, (nbits + 7) / 8) });
+}
+/// bytes -> `nbits` <= 8 nbytes bytes of 0 / 1
+pub fn unpack(ctx: &Context, bytes_dev: *const u8, nbytes: usize, order: i32, bits_dev: *mut u8, nbits: usize) {
+    check(unsafe { aeth_bits_unpack(ctx.h, bytes_dev, nbytes, order, bits_dev, nbits) });
+}
+
 /// OFDM symbols (no body in the reference: it has `Fft`, `vec_mul` and `chunks_mut(fft_len)` framing only): a transform
 /// length, a cyclic prefix and a carrier list (`bins[k]`: the FFT bin of carrier k).  `demod` strips the prefix, transforms
 /// with the sign of `Fft::fwd`, picks the carriers and multiplies by `eq[k]` in one kernel; `modulate` is the way back with
