@@ -291,6 +291,19 @@ PROTOTYPES = {
     "aeth_crc_check": (i32, [vp, vp, sz, sz, u64, vp, vp, vp]),
     "aeth_bits_pack": (i32, [vp, vp, sz, i32, vp, sz]),
     "aeth_bits_unpack": (i32, [vp, vp, sz, i32, vp, sz]),
+    "aeth_ldpc_generator": (i32, [vp, vp, sz]),
+    "aeth_ldpc_create": (i32, [vp, vp, pvp]),
+    "aeth_ldpc_destroy": (i32, [vp]),
+    "aeth_ldpc_n": (sz, [vp]),
+    "aeth_ldpc_k": (sz, [vp]),
+    "aeth_ldpc_rows": (C.c_uint32, [vp]),
+    "aeth_ldpc_cols": (C.c_uint32, [vp]),
+    "aeth_ldpc_z": (C.c_uint32, [vp]),
+    "aeth_ldpc_edges": (sz, [vp]),
+    "aeth_ldpc_lds_bytes": (sz, [vp]),
+    "aeth_ldpc_group": (C.c_uint32, [vp]),
+    "aeth_ldpc_encode": (i32, [vp, vp, sz, vp, sz]),
+    "aeth_ldpc_decode": (i32, [vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp]),
 }
 
 _lib = None

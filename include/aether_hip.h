@@ -57,7 +57,8 @@ typedef struct aeth_arb aeth_arb;       /* arbitrary-ratio resampler: interpolat
 typedef struct aeth_cc aeth_cc;         /* convolutional code: encoder and block-wise soft-decision Viterbi decoder */
 typedef struct aeth_remap aeth_remap;   /* rate matching: a periodic byte map (puncture, depuncture, interleave, chains) */
 typedef struct aeth_crc aeth_crc;       /* frame checks: a CRC of width 1 .. 64 over bit frames: registers, attach, check */
-typedef struct aeth_ofdm aeth_ofdm;     /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
+typedef struct aeth_ldpc aeth_ldpc;     /* quasi-cyclic LDPC code: systematic encoder and layered integer min-sum decoder */
+typedef struct aeth_ofdm aeth_ofdm;    /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
 
@@ -1204,6 +1205,77 @@ AETH_API int aeth_crc_check(aeth_crc *crc, const uint8_t *in_dev, size_t L, size
                             aeth_crc_summary *summary_dev);
 AETH_API int aeth_bits_pack(aeth_ctx *ctx, const uint8_t *bits_dev, size_t nbits, int order, uint8_t *bytes_dev, size_t nbytes);
 AETH_API int aeth_bits_unpack(aeth_ctx *ctx, const uint8_t *bytes_dev, size_t nbytes, int order, uint8_t *bits_dev, size_t nbits);
+
+/* ---- LDPC codes: quasi-cyclic encoder and a layered min-sum decoder (no body in the reference) ---- */
+/* The block code of 802.11n/ac/ax, 5G NR data and DVB-S2, behind aeth_demod_soft.  Everything is integer arithmetic and
+ * defined byte for byte.
+ *
+ * The code.  aeth_ldpc_code is a table of rows x cols circulant blocks of size z, row-major: shift[r cols + c] is -1 for
+ * a zero block, else s in [0, z): the z x z identity shifted so that row i of the block has its one at column
+ * (i + s) mod z.  N = cols z, M = rows z, K = N - M.  Bits are one byte per bit (taken & 1); soft values are int8_t,
+ * positive means bit 0 is likelier and 0 is an erasure (aeth_cc_decode, aeth_demod_soft).  Punctured and shortened
+ * positions are the caller's job with aeth_remap_exec (fill 0 or 127).
+ *
+ * Limits, all refused before any device work with the offending value in the message: 1 <= rows < cols, rows <= 256,
+ * 1 <= z (AETH_E_ARG); every entry in [-1, z) (the message names position and value); every row holds at least one
+ * block (the message names the row); the decoder state of 2 N + E z bytes, E the number of non-negative entries, is at
+ * most 64 KiB (AETH_E_UNSUPPORTED, naming both numbers); the parity part -- the last `rows` block columns as a dense
+ * M x M matrix over GF(2) -- is invertible (AETH_E_ARG, "parity part singular").  A refused create leaves the device's
+ * free memory unchanged.
+ *
+ * Encoder, systematic: coded[f N .. f N + K) = u_f & 1, then the M parity bits p = P u over GF(2), where H = [A | B] and
+ * P = B^-1 A (M x K), computed once at create on the host by Gaussian elimination on 64-bit words.
+ * aeth_ldpc_generator is a host function with no context: row i of P in ceil(K / 64) words, bit j at word j / 64, bit
+ * j % 64; nwords below M ceil(K / 64) is AETH_E_LEN.  aeth_ldpc_create uploads P; the object owns P and the shift table
+ * on the device.  aeth_ldpc_encode: nbits = F K and ncoded = F N, else AETH_E_LEN; any byte alignment; overlapping ranges
+ * AETH_E_ARG; F = 0 launches nothing.
+ *
+ * Decoder: layered normalised min-sum, all arithmetic int32.  Per codeword Q[v] = soft[v] for v < N and R[e] = 0 for
+ * every edge.  The edges of check (r, i) are the columns c ascending with shift[r][c] >= 0, at variable
+ * v = c z + (i + shift[r][c]) mod z.  One iteration visits the layers r = 0 .. rows - 1 in order; for every check (r, i)
+ * of the layer:
+ *     1. T_e = Q[v_e] - R[e];  neg_e = T_e < 0 (zero counts as positive)
+ *     2. m1 <= m2 are the two smallest |T_e|; both start at 32767, and a value replaces m1 only if strictly smaller, so
+ *        the first of equal minima is the argmin a
+ *     3. mag_e = min((3 (e == a ? m2 : m1)) >> 2, 127)
+ *     4. R[e] = (parity of all neg) xor neg_e ? -mag_e : mag_e
+ *     5. Q[v_e] = T_e + R[e]
+ * The checks of a layer touch disjoint variables, so their order does not matter; layers are ordered.  Nothing
+ * saturates: Q = soft + sum R throughout, so |Q| <= 128 + 127 rows < 2^15, which is why rows <= 256.
+ * After each full iteration `unsat` is the number of checks whose hard decisions (Q[v] < 0) have odd parity; with
+ * AETH_LDPC_EARLY the codeword stops when unsat == 0.  max_iter = 0 is allowed: the hard decisions of the input and
+ * their unsat.  Output bits are Q[v] < 0 for all N positions, with AETH_LDPC_PAYLOAD only the first K.  rec_dev (may be
+ * NULL; 4-byte aligned, AETH_E_ALIGN) receives {iterations run, unsat after the last} per codeword.
+ * aeth_ldpc_decode: nsoft = F N, nbits = F N or F K by flag, else AETH_E_LEN; max_iter > 1000, unknown flag bits, ranges
+ * that share a byte AETH_E_ARG; any byte alignment of soft and bits.  Codewords are independent: a call cut at any
+ * codeword equals two calls byte for byte, and nothing depends on aeth_ldpc_group.
+ *
+ * Kernel.  aeth_ldpc_group codewords share a workgroup -- as many as keep G z <= 256 lanes and G states within 64 KiB of
+ * LDS (aeth_ldpc_lds_bytes), at least one; a lane owns one check of the current layer; Q is int16 and R int8 in LDS; one
+ * workgroup barrier per layer.  Getters return 0 for NULL and aeth_ldpc_destroy(NULL) is AETH_OK.  All device calls are
+ * ordered on the context's stream and none waits.
+ *
+ * Not built: codes above the 64 KiB LDS state (5G base graph 1 at large Z), standard base-matrix catalogues, soft
+ * (posterior) output, offset min-sum, a structured encoder that avoids the dense P, an aeth_stream_op kind, host-slice
+ * flavours. */
+#define AETH_LDPC_EARLY 1u
+#define AETH_LDPC_PAYLOAD 2u
+typedef struct aeth_ldpc_code { uint32_t rows, cols, z; const int32_t *shift; } aeth_ldpc_code;   /* shift[rows*cols], row-major */
+typedef struct aeth_ldpc_record { uint32_t iterations, unsatisfied; } aeth_ldpc_record;
+AETH_API int aeth_ldpc_generator(const aeth_ldpc_code *code, uint64_t *p_out, size_t nwords);
+AETH_API int aeth_ldpc_create(aeth_ctx *ctx, const aeth_ldpc_code *code, aeth_ldpc **out);
+AETH_API int aeth_ldpc_destroy(aeth_ldpc *ldpc);
+AETH_API size_t aeth_ldpc_n(const aeth_ldpc *ldpc);
+AETH_API size_t aeth_ldpc_k(const aeth_ldpc *ldpc);
+AETH_API uint32_t aeth_ldpc_rows(const aeth_ldpc *ldpc);
+AETH_API uint32_t aeth_ldpc_cols(const aeth_ldpc *ldpc);
+AETH_API uint32_t aeth_ldpc_z(const aeth_ldpc *ldpc);
+AETH_API size_t aeth_ldpc_edges(const aeth_ldpc *ldpc);
+AETH_API size_t aeth_ldpc_lds_bytes(const aeth_ldpc *ldpc);     /* dynamic LDS of a decoder workgroup */
+AETH_API uint32_t aeth_ldpc_group(const aeth_ldpc *ldpc);       /* codewords per decoder workgroup */
+AETH_API int aeth_ldpc_encode(aeth_ldpc *ldpc, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded);
+AETH_API int aeth_ldpc_decode(aeth_ldpc *ldpc, const int8_t *soft_dev, size_t nsoft, uint32_t max_iter, uint32_t flags,
+                              uint8_t *bits_dev, size_t nbits, aeth_ldpc_record *rec_dev);
 
 /* ---- OFDM symbols (no body in the reference: it has Fft, VecOps::vec_mul and chunks_mut(fft_len) framing only) ---- */
 /* The framing and the one-tap equaliser of an OFDM link; everything else such a link needs is above (aeth_seq_scramble,

@@ -19,6 +19,11 @@ pub const AETH_REMAP_ROUTE_TILE: c_int = 1; pub const AETH_REMAP_ROUTE_GATHER: c
 pub const AETH_CRC_ROUTE_FRAMES: c_int = 1; pub const AETH_CRC_ROUTE_LONG: c_int = 2;
 pub const AETH_BITS_LSB_FIRST: c_int = 0; pub const AETH_BITS_MSB_FIRST: c_int = 1;
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_crc_summary { pub n_bad: u64, pub first_bad: u64 }
+#[repr(C)] pub struct aeth_ldpc { _p: [u8; 0] }
+pub const AETH_LDPC_EARLY: u32 = 1; pub const AETH_LDPC_PAYLOAD: u32 = 2;
+/// aeth_ldpc_code: rows x cols circulant blocks of size z; shift[rows * cols], row-major, -1 for a zero block
+#[repr(C)] #[derive(Clone, Copy)] pub struct aeth_ldpc_code { pub rows: u32, pub cols: u32, pub z: u32, pub shift: *const i32 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_ldpc_record { pub iterations: u32, pub unsatisfied: u32 }
 #[repr(C)] pub struct aeth_ofdm { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
@@ -364,6 +369,20 @@ extern "C" {
                           payload_dev: *mut u8, summary_dev: *mut aeth_crc_summary) -> c_int;
     pub fn aeth_bits_pack(ctx: *mut aeth_ctx, bits_dev: *const u8, nbits: usize, order: c_int, bytes_dev: *mut u8, nbytes: usize) -> c_int;
     pub fn aeth_bits_unpack(ctx: *mut aeth_ctx, bytes_dev: *const u8, nbytes: usize, order: c_int, bits_dev: *mut u8, nbits: usize) -> c_int;
+    pub fn aeth_ldpc_generator(code: *const aeth_ldpc_code, p_out: *mut u64, nwords: usize) -> c_int;
+    pub fn aeth_ldpc_create(ctx: *mut aeth_ctx, code: *const aeth_ldpc_code, out: *mut *mut aeth_ldpc) -> c_int;
+    pub fn aeth_ldpc_destroy(ldpc: *mut aeth_ldpc) -> c_int;
+    pub fn aeth_ldpc_n(ldpc: *const aeth_ldpc) -> usize;
+    pub fn aeth_ldpc_k(ldpc: *const aeth_ldpc) -> usize;
+    pub fn aeth_ldpc_rows(ldpc: *const aeth_ldpc) -> u32;
+    pub fn aeth_ldpc_cols(ldpc: *const aeth_ldpc) -> u32;
+    pub fn aeth_ldpc_z(ldpc: *const aeth_ldpc) -> u32;
+    pub fn aeth_ldpc_edges(ldpc: *const aeth_ldpc) -> usize;
+    pub fn aeth_ldpc_lds_bytes(ldpc: *const aeth_ldpc) -> usize;
+    pub fn aeth_ldpc_group(ldpc: *const aeth_ldpc) -> u32;
+    pub fn aeth_ldpc_encode(ldpc: *mut aeth_ldpc, bits_dev: *const u8, nbits: usize, coded_dev: *mut u8, ncoded: usize) -> c_int;
+    pub fn aeth_ldpc_decode(ldpc: *mut aeth_ldpc, soft_dev: *const i8, nsoft: usize, max_iter: u32, flags: u32, bits_dev: *mut u8,
+                            nbits: usize, rec_dev: *mut aeth_ldpc_record) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;
