@@ -304,6 +304,20 @@ PROTOTYPES = {
     "aeth_ldpc_group": (C.c_uint32, [vp]),
     "aeth_ldpc_encode": (i32, [vp, vp, sz, vp, sz]),
     "aeth_ldpc_decode": (i32, [vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp]),
+    "aeth_rs_named": (i32, [C.c_char_p, vp]),
+    "aeth_rs_generator": (i32, [vp, vp, sz]),
+    "aeth_rs_host_encode": (i32, [vp, vp, sz, C.c_uint32, vp, sz]),
+    "aeth_rs_host_decode": (i32, [vp, vp, sz, vp, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
+    "aeth_rs_create": (i32, [vp, vp, pvp]),
+    "aeth_rs_destroy": (i32, [vp]),
+    "aeth_rs_n": (sz, [vp]),
+    "aeth_rs_k": (sz, [vp]),
+    "aeth_rs_nroots": (C.c_uint32, [vp]),
+    "aeth_rs_m": (C.c_uint32, [vp]),
+    "aeth_rs_group": (C.c_uint32, [vp]),
+    "aeth_rs_lds_bytes": (sz, [vp, C.c_uint32]),
+    "aeth_rs_encode": (i32, [vp, vp, sz, C.c_uint32, vp, sz]),
+    "aeth_rs_decode": (i32, [vp, vp, sz, vp, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
 }
 
 _lib = None

@@ -57,6 +57,7 @@ typedef struct aeth_arb aeth_arb;       /* arbitrary-ratio resampler: interpolat
 typedef struct aeth_cc aeth_cc;         /* convolutional code: encoder and block-wise soft-decision Viterbi decoder */
 typedef struct aeth_remap aeth_remap;   /* rate matching: a periodic byte map (puncture, depuncture, interleave, chains) */
 typedef struct aeth_crc aeth_crc;       /* frame checks: a CRC of width 1 .. 64 over bit frames: registers, attach, check */
+typedef struct aeth_rs aeth_rs;         /* Reed-Solomon code over GF(2^m): systematic encoder, errors-and-erasures decoder */
 typedef struct aeth_ldpc aeth_ldpc;     /* quasi-cyclic LDPC code: systematic encoder and layered integer min-sum decoder */
 typedef struct aeth_ofdm aeth_ofdm;    /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
@@ -1276,6 +1277,75 @@ AETH_API uint32_t aeth_ldpc_group(const aeth_ldpc *ldpc);       /* codewords per
 AETH_API int aeth_ldpc_encode(aeth_ldpc *ldpc, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded);
 AETH_API int aeth_ldpc_decode(aeth_ldpc *ldpc, const int8_t *soft_dev, size_t nsoft, uint32_t max_iter, uint32_t flags,
                               uint8_t *bits_dev, size_t nbits, aeth_ldpc_record *rec_dev);
+
+/* ---- Reed-Solomon codes: systematic encoder, errors-and-erasures decoder (no body in the reference) ---- */
+/* The outer code of CCSDS telemetry (RS(255, 223) around the K = 7 code of aeth_cc_*), of DVB-S / DVB-T (RS(204, 188)),
+ * of DAB+, ATSC, DSL, CD/DVD, QR codes and RAID-6: the code over symbols that repairs the bursts a Viterbi decoder
+ * leaves.  Everything is integer arithmetic and defined byte for byte.
+ *
+ * The code.  Symbols are bytes over GF(2^m), 3 <= m <= 8, N0 = 2^m - 1; every input byte is taken & N0.  poly is the
+ * field polynomial with its x^m term (0x11d, 0x187, 0x13, 0xb) and must be primitive (x has order N0), else AETH_E_ARG
+ * "polynomial not primitive".  beta = alpha^prim with gcd(prim, N0) = 1, 0 <= fcr < N0, and
+ *     g(x) = prod over j < r of (x - beta^(fcr + j)),  r = nroots,  1 <= r <= 64,  r < n <= N0,  k = n - r;
+ * n < N0 is the shortened code.  r > 64 is AETH_E_UNSUPPORTED, every other violation AETH_E_ARG, refused before any
+ * device work with the offending value in the message.  Symbol 0 of a codeword is the highest coefficient and is
+ * transmitted first: c(x) = sum c_j x^(n-1-j).  A codeword is k data symbols followed by r parity symbols, the remainder
+ * of d(x) x^r modulo g.
+ * Interleaving is an argument of every call: depth I, 1 <= I <= 64.  A frame is I n bytes (I k on the data side); symbol
+ * j of codeword i of frame f sits at byte f I n + j I + i.  I = 1 is plain contiguous codewords, I = 4 or 5 the CCSDS
+ * frame.  The data part of an encoded frame is the input frame in place (& N0) and the I r parity bytes follow it.
+ * aeth_rs_named (host only) knows ccsds-255-223 (0x187, fcr 112, prim 11; conventional basis), ccsds-255-239 (fcr 120),
+ * dvb-204-188 (0x11d, fcr 0, prim 1) and rs-15-11 (0x13, fcr 1); an unknown name is AETH_E_ARG and the message lists the
+ * known ones.
+ *
+ * Host functions with no context: aeth_rs_generator writes g_out[i] = the coefficient of x^i, i <= r (ng < r + 1 is
+ * AETH_E_LEN); aeth_rs_host_encode and aeth_rs_host_decode run the definition on host memory with the rules of the
+ * device calls (their record and summary pointers need no alignment).
+ *
+ * Decode, per codeword.  E is the set of erased positions (era[pos] != 0; era_dev is NULL or as long as the input),
+ * f = |E|.  For a codeword c of the (shortened) code e(c) is the number of positions outside E where c differs from the
+ * masked input.  If some c has 2 e(c) + f <= r it is unique, and the output is c (its first k symbols with
+ * AETH_RS_PAYLOAD) with the record {corrected = the number of all n positions where c differs from the masked input,
+ * status = 0}.  Otherwise the output is the masked input (or its first k symbols) and the record is {0, 1}; f > r is
+ * such a failure, not an error.  The decoder establishes the bound itself: it fails unless deg Lambda = L,
+ * 2 (L - f) + f <= r, Lambda has exactly deg Lambda distinct roots, all at positions below n, and no Forney
+ * denominator vanishes.  rec_dev (may be NULL; 4-byte aligned) receives one record per codeword, codeword i of frame f
+ * at f I + i.  summary_dev (may be NULL; 8-byte aligned) receives {n_failed, n_corrected}: written, not accumulated,
+ * by a fixed fold of per-workgroup records and so the same in every run.
+ *
+ * Call rules.  Codewords are independent: a call cut at any frame equals two calls byte for byte.  Lengths are whole
+ * frames and the same number of them on both sides (AETH_E_LEN); ranges that share a byte, unknown flags, depth outside
+ * 1 .. 64 AETH_E_ARG; rec_dev or summary_dev misaligned AETH_E_ALIGN; data pointers may have any byte alignment.  Zero
+ * frames launch nothing but decode still writes the summary {0, 0}.  All device calls are ordered on the context's
+ * stream and none waits.  Getters return 0 for NULL and aeth_rs_destroy(NULL) is AETH_OK.
+ *
+ * Kernel.  A codeword belongs to a group of R2 lanes, R2 the power of two at or above r; aeth_rs_group = 256 / R2
+ * codewords share a workgroup.  Encoder and syndromes multiply by a per-lane constant with eight select-XORs on the
+ * constant's images in two registers; only damaged codewords run erasure locator, Berlekamp-Massey, Chien and Forney,
+ * on log / antilog tables and aeth_rs_lds_bytes(rs, depth) bytes of dynamic LDS per workgroup.
+ *
+ * Not built: the CCSDS dual-basis representation, symbols wider than 8 bits, BCH codes over GF(2), a convolutional
+ * (Forney) byte interleaver, soft-decision decoding, an aeth_stream_op kind and host-slice flavours. */
+#define AETH_RS_PAYLOAD 1u
+typedef struct aeth_rs_code { uint32_t m, poly, fcr, prim, nroots, n; } aeth_rs_code;
+typedef struct aeth_rs_record { uint32_t corrected, status; } aeth_rs_record;
+typedef struct aeth_rs_summary { uint64_t n_failed; uint64_t n_corrected; } aeth_rs_summary;
+AETH_API int aeth_rs_named(const char *name, aeth_rs_code *code);
+AETH_API int aeth_rs_generator(const aeth_rs_code *code, uint8_t *g_out, size_t ng);
+AETH_API int aeth_rs_host_encode(const aeth_rs_code *code, const uint8_t *data_host, size_t ndata, uint32_t depth, uint8_t *coded_host, size_t ncoded);
+AETH_API int aeth_rs_host_decode(const aeth_rs_code *code, const uint8_t *in_host, size_t nin, const uint8_t *era_host, uint32_t depth,
+                                 uint32_t flags, uint8_t *out_host, size_t nout, aeth_rs_record *rec_host, aeth_rs_summary *summary_host);
+AETH_API int aeth_rs_create(aeth_ctx *ctx, const aeth_rs_code *code, aeth_rs **out);
+AETH_API int aeth_rs_destroy(aeth_rs *rs);
+AETH_API size_t aeth_rs_n(const aeth_rs *rs);
+AETH_API size_t aeth_rs_k(const aeth_rs *rs);
+AETH_API uint32_t aeth_rs_nroots(const aeth_rs *rs);
+AETH_API uint32_t aeth_rs_m(const aeth_rs *rs);
+AETH_API uint32_t aeth_rs_group(const aeth_rs *rs);                  /* codewords per workgroup */
+AETH_API size_t aeth_rs_lds_bytes(const aeth_rs *rs, uint32_t depth);   /* dynamic LDS of a decoder workgroup */
+AETH_API int aeth_rs_encode(aeth_rs *rs, const uint8_t *data_dev, size_t ndata, uint32_t depth, uint8_t *coded_dev, size_t ncoded);
+AETH_API int aeth_rs_decode(aeth_rs *rs, const uint8_t *in_dev, size_t nin, const uint8_t *era_dev, uint32_t depth, uint32_t flags,
+                            uint8_t *out_dev, size_t nout, aeth_rs_record *rec_dev, aeth_rs_summary *summary_dev);
 
 /* ---- OFDM symbols (no body in the reference: it has Fft, VecOps::vec_mul and chunks_mut(fft_len) framing only) ---- */
 /* The framing and the one-tap equaliser of an OFDM link; everything else such a link needs is above (aeth_seq_scramble,

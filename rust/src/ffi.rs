@@ -24,6 +24,12 @@ pub const AETH_LDPC_EARLY: u32 = 1; pub const AETH_LDPC_PAYLOAD: u32 = 2;
 /// aeth_ldpc_code: rows x cols circulant blocks of size z; shift[rows * cols], row-major, -1 for a zero block
 #[repr(C)] #[derive(Clone, Copy)] pub struct aeth_ldpc_code { pub rows: u32, pub cols: u32, pub z: u32, pub shift: *const i32 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_ldpc_record { pub iterations: u32, pub unsatisfied: u32 }
+#[repr(C)] pub struct aeth_rs { _p: [u8; 0] }
+pub const AETH_RS_PAYLOAD: u32 = 1;
+/// aeth_rs_code: RS(n, n - nroots) over GF(2^m); poly carries its x^m term
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_rs_code { pub m: u32, pub poly: u32, pub fcr: u32, pub prim: u32, pub nroots: u32, pub n: u32 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_rs_record { pub corrected: u32, pub status: u32 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_rs_summary { pub n_failed: u64, pub n_corrected: u64 }
 #[repr(C)] pub struct aeth_ofdm { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
@@ -383,6 +389,22 @@ extern "C" {
     pub fn aeth_ldpc_encode(ldpc: *mut aeth_ldpc, bits_dev: *const u8, nbits: usize, coded_dev: *mut u8, ncoded: usize) -> c_int;
     pub fn aeth_ldpc_decode(ldpc: *mut aeth_ldpc, soft_dev: *const i8, nsoft: usize, max_iter: u32, flags: u32, bits_dev: *mut u8,
                             nbits: usize, rec_dev: *mut aeth_ldpc_record) -> c_int;
+    pub fn aeth_rs_named(name: *const c_char, code: *mut aeth_rs_code) -> c_int;
+    pub fn aeth_rs_generator(code: *const aeth_rs_code, g_out: *mut u8, ng: usize) -> c_int;
+    pub fn aeth_rs_host_encode(code: *const aeth_rs_code, data_host: *const u8, ndata: usize, depth: u32, coded_host: *mut u8, ncoded: usize) -> c_int;
+    pub fn aeth_rs_host_decode(code: *const aeth_rs_code, in_host: *const u8, nin: usize, era_host: *const u8, depth: u32, flags: u32,
+                               out_host: *mut u8, nout: usize, rec_host: *mut aeth_rs_record, summary_host: *mut aeth_rs_summary) -> c_int;
+    pub fn aeth_rs_create(ctx: *mut aeth_ctx, code: *const aeth_rs_code, out: *mut *mut aeth_rs) -> c_int;
+    pub fn aeth_rs_destroy(rs: *mut aeth_rs) -> c_int;
+    pub fn aeth_rs_n(rs: *const aeth_rs) -> usize;
+    pub fn aeth_rs_k(rs: *const aeth_rs) -> usize;
+    pub fn aeth_rs_nroots(rs: *const aeth_rs) -> u32;
+    pub fn aeth_rs_m(rs: *const aeth_rs) -> u32;
+    pub fn aeth_rs_group(rs: *const aeth_rs) -> u32;
+    pub fn aeth_rs_lds_bytes(rs: *const aeth_rs, depth: u32) -> usize;
+    pub fn aeth_rs_encode(rs: *mut aeth_rs, data_dev: *const u8, ndata: usize, depth: u32, coded_dev: *mut u8, ncoded: usize) -> c_int;
+    pub fn aeth_rs_decode(rs: *mut aeth_rs, in_dev: *const u8, nin: usize, era_dev: *const u8, depth: u32, flags: u32, out_dev: *mut u8,
+                          nout: usize, rec_dev: *mut aeth_rs_record, summary_dev: *mut aeth_rs_summary) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;
