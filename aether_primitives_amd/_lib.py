@@ -318,6 +318,17 @@ PROTOTYPES = {
     "aeth_rs_lds_bytes": (sz, [vp, C.c_uint32]),
     "aeth_rs_encode": (i32, [vp, vp, sz, C.c_uint32, vp, sz]),
     "aeth_rs_decode": (i32, [vp, vp, sz, vp, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
+    "aeth_polar_rank": (i32, [C.c_uint32, vp, sz]),
+    "aeth_polar_mask": (i32, [C.c_uint32, C.c_uint32, vp, sz]),
+    "aeth_polar_create": (i32, [vp, C.c_uint32, vp, pvp]),
+    "aeth_polar_destroy": (i32, [vp]),
+    "aeth_polar_n": (sz, [vp]),
+    "aeth_polar_k": (sz, [vp]),
+    "aeth_polar_lanes": (C.c_uint32, [vp]),
+    "aeth_polar_group": (C.c_uint32, [vp]),
+    "aeth_polar_lds_bytes": (sz, [vp]),
+    "aeth_polar_encode": (i32, [vp, vp, sz, vp, sz]),
+    "aeth_polar_decode": (i32, [vp, vp, sz, vp, C.c_uint32, vp, sz, vp]),
 }
 
 _lib = None

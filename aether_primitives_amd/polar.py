@@ -1,0 +1,121 @@
+"""Polar codes on the device: the encoder and a successive-cancellation decoder with one bit flip per codeword
+(include/aether_hip.h, aeth_polar_*).
+
+The reference has nothing of the kind.  A code is N = 2^n positions, 3 <= n <= 10, and a mask of N bytes: 1 where a
+position carries information, 0 where it is frozen.  `rank(n)` orders the positions by an integer polarization weight and
+`mask(n, K)` marks the K most reliable; any other mask (the 5G sequence, a design for one SNR) is passed as it is.  Bits
+are one byte per bit, soft values int8 with the convention of `demod_soft` (positive: bit 0).  `decode` returns the K
+information decisions (or the N re-encoded bits) and, per codeword, a record of the four least reliable information
+decisions: the candidates of a CRC-aided SC-Flip decoder, which decodes the frames `Crc.check` calls bad again with
+`flip = index[r]` (examples/polar.py).  Only verdicts, records and payloads have to leave the device."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from ._records import DeviceRecordArray
+from .modulation import DeviceBits, DeviceSoft
+
+CODEWORD = 1                                    # AETH_POLAR_CODEWORD
+NONE = 0xFFFFFFFF                               # AETH_POLAR_NONE
+MIN_N, MAX_N = 3, 10
+
+RECORD = np.dtype([("index", np.uint32, 4), ("abs", np.uint32, 4)])
+
+
+def rank(n):
+    """the 2^n positions, most reliable first (host only)"""
+    out = np.zeros(1 << n if MIN_N <= n <= MAX_N else 1, np.uint32)
+    check(_lib.load().aeth_polar_rank(int(n), out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+def mask(n, K):
+    """uint8 [2^n]: 1 at the K most reliable positions of `rank(n)` (host only)"""
+    out = np.zeros(1 << n if MIN_N <= n <= MAX_N else 1, np.uint8)
+    check(_lib.load().aeth_polar_mask(int(n), int(K), out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+class DeviceRecords(DeviceRecordArray):
+    """Device-resident `[aeth_polar_record]`; `.to_host()` -> structured array with `index` and `abs`, four each."""
+
+    DTYPE = RECORD
+
+
+class DeviceFlips:
+    """Device-resident `[u32]`: one flip position per codeword."""
+
+    def __init__(self, ctx, n, host=None):
+        self.ctx, self.n = ctx, int(n)
+        self.ptr = ctx.alloc(max(self.n, 1) * 4)
+        if host is not None and self.n:
+            ctx.upload(self.ptr, np.ascontiguousarray(host, np.uint32))
+
+    def __len__(self):
+        return self.n
+
+    def __del__(self):
+        try:
+            if self.ptr and self.ctx.h:
+                self.ctx.free(self.ptr); self.ptr = None
+        except Exception:
+            pass
+
+
+class Polar:
+    """Polar(ctx, n, mask): the object owns the decoder's schedule and the position tables on the device."""
+
+    def __init__(self, ctx, n, mask):
+        self.ctx = ctx
+        self._lib = _lib.load()
+        self.h = C.c_void_p()
+        m = np.ascontiguousarray(mask, np.uint8)
+        assert m.size == (1 << n if MIN_N <= n <= MAX_N else m.size), "the mask holds 2^n bytes"
+        check(self._lib.aeth_polar_create(ctx.h, int(n), m.ctypes.data_as(C.c_void_p), C.byref(self.h)))
+        self.mask = m.copy()
+
+    n = property(lambda self: int(self._lib.aeth_polar_n(self.h)))
+    k = property(lambda self: int(self._lib.aeth_polar_k(self.h)))
+    lanes = property(lambda self: int(self._lib.aeth_polar_lanes(self.h)))
+    group = property(lambda self: int(self._lib.aeth_polar_group(self.h)))
+    lds_bytes = property(lambda self: int(self._lib.aeth_polar_lds_bytes(self.h)))
+
+    def encode(self, bits, out=None):
+        """F K information bits -> F N coded bits"""
+        if not isinstance(bits, DeviceBits):
+            bits = DeviceBits(self.ctx, np.asarray(bits).size, bits)
+        F = bits.n // self.k
+        if out is None:
+            out = DeviceBits(self.ctx, F * self.n)
+        check(self._lib.aeth_polar_encode(self.h, C.c_void_p(bits.ptr), bits.n, C.c_void_p(out.ptr), out.n))
+        return out
+
+    def decode(self, soft, flip=None, codeword=False, records=True, out=None):
+        """F N soft values -> (DeviceBits of F K decisions, or the F N re-encoded bits with codeword=True; DeviceRecords or
+        None).  flip: None, a `DeviceFlips` or F host positions, one per codeword (NONE: no flip)."""
+        if not isinstance(soft, DeviceSoft):
+            soft = DeviceSoft(self.ctx, np.asarray(soft).size, soft)
+        F = soft.n // self.n
+        if flip is not None and not isinstance(flip, DeviceFlips):
+            flip = DeviceFlips(self.ctx, np.asarray(flip).size, flip)
+        assert flip is None or flip.n == F, "one flip position per codeword"
+        if out is None:
+            out = DeviceBits(self.ctx, F * (self.n if codeword else self.k))
+        rec = DeviceRecords(self.ctx, F) if records else None
+        check(self._lib.aeth_polar_decode(self.h, C.c_void_p(soft.ptr), soft.n, C.c_void_p(flip.ptr) if flip is not None else None,
+                                          CODEWORD if codeword else 0, C.c_void_p(out.ptr), out.n, rec._p() if rec is not None else None))
+        return out, rec
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            if self.ctx.h:                                           # a closed context has taken the stream with it
+                self._lib.aeth_polar_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

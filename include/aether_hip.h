@@ -59,6 +59,7 @@ typedef struct aeth_remap aeth_remap;   /* rate matching: a periodic byte map (p
 typedef struct aeth_crc aeth_crc;       /* frame checks: a CRC of width 1 .. 64 over bit frames: registers, attach, check */
 typedef struct aeth_rs aeth_rs;         /* Reed-Solomon code over GF(2^m): systematic encoder, errors-and-erasures decoder */
 typedef struct aeth_ldpc aeth_ldpc;     /* quasi-cyclic LDPC code: systematic encoder and layered integer min-sum decoder */
+typedef struct aeth_polar aeth_polar;   /* polar code: encoder and successive-cancellation decoder with a flip and candidate records */
 typedef struct aeth_ofdm aeth_ofdm;    /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
@@ -1346,6 +1347,78 @@ AETH_API size_t aeth_rs_lds_bytes(const aeth_rs *rs, uint32_t depth);   /* dynam
 AETH_API int aeth_rs_encode(aeth_rs *rs, const uint8_t *data_dev, size_t ndata, uint32_t depth, uint8_t *coded_dev, size_t ncoded);
 AETH_API int aeth_rs_decode(aeth_rs *rs, const uint8_t *in_dev, size_t nin, const uint8_t *era_dev, uint32_t depth, uint32_t flags,
                             uint8_t *out_dev, size_t nout, aeth_rs_record *rec_dev, aeth_rs_summary *summary_dev);
+
+/* ---- Polar codes: encoder, successive-cancellation decoder with bit flips (no body in the reference) ---- */
+/* The code of the 5G NR control channels (PDCCH, PBCH, PUCCH) and the short-block code (N <= 1024) that LDPC serves
+ * badly, behind aeth_demod_soft and aeth_remap and in front of aeth_crc_check.  Everything is integer arithmetic and
+ * defined byte for byte.
+ *
+ * The code.  N = 2^n with 3 <= n <= 10.  mask is N bytes on the host, each 0 (frozen) or 1 (information); K is the
+ * number of ones, 1 <= K <= N.  Bits are one byte per bit, taken & 1.  Soft values are int8_t; positive means bit 0 is
+ * likelier and 0 is an erasure, as in aeth_cc_decode and aeth_ldpc_decode.  Punctured positions enter as 0 and shortened
+ * positions as +127, both through aeth_remap.
+ *
+ * Transform (natural order, no bit reversal; the 5G convention):
+ *     x = u; for s = 0 .. n - 1: for every i with bit s of i clear: x[i] ^= x[i + 2^s].
+ *
+ * Encoder.  u[i] = 0 where mask[i] = 0; the K information bits of a codeword go to the ones of the mask in ascending i;
+ * coded = transform(u).  nbits = F K and ncoded = F N, anything else is AETH_E_LEN; any byte alignment; overlapping
+ * ranges AETH_E_ARG; F = 0 launches nothing.
+ *
+ * Decoder: successive cancellation with the min-sum f, all arithmetic int32.  Nothing saturates: a value d levels below
+ * the channel is at most 128 * 2^d in magnitude, below 2^18.  dec(L[0..m), base):
+ *     m = 1, the leaf i = base: frozen: u[i] = 0; information: u[i] = (L[0] < 0), inverted if i == flip.  Returns [u[i]].
+ *     m > 1, h = m / 2, a = L[0..h), b = L[h..m):
+ *         x1 = dec(f(a, b), base),  f(a, b) = sgn(a) sgn(b) min(|a|, |b|), 0 when either argument is 0
+ *         x2 = dec(g, base + h),    g[j] = b[j] + a[j] if x1[j] == 0, else b[j] - a[j]
+ *         returns [x1 ^ x2 | x2]
+ * The codeword's result is dec(soft as int32, 0); its return value is the re-encoded decision x^.
+ * flip_dev may be NULL; otherwise F uint32_t, 4-byte aligned (else AETH_E_ALIGN), one position per codeword.
+ * AETH_POLAR_NONE, a frozen position or a value >= N never matches an information leaf: all three are legal and have no
+ * effect, so device data needs no validation.  The output is the K information decisions in ascending i, with
+ * AETH_POLAR_CODEWORD the N bits of x^.  Codewords are independent: a call cut at any codeword equals two calls byte for
+ * byte, and nothing depends on the grouping getters.
+ *
+ * Record.  rec_dev may be NULL; 4-byte aligned, one aeth_polar_record per codeword: the four information leaves with the
+ * least (|L|, i) in lexicographic order, ascending, L the value the leaf decided on in this pass; slots beyond K hold
+ * 0xFFFFFFFF in both fields.  These are the SC-Flip candidates: decode, check the CRC (aeth_crc_check), and decode the
+ * failed frames again with flip = index[r].
+ *
+ * Construction (host, no context).  aeth_polar_rank writes the N positions, most reliable first, by the integer
+ * polarization weight W(i) = sum over j of bit_j(i) (q[j mod 4] << (j div 4)),
+ * q = {4294967296, 5107605667, 6074001000, 7223245206} = round(2^(r/4) 2^32): larger W first, ties to the larger i
+ * (there are none for n <= 10).  n = 3 gives 7 6 5 3 4 2 1 0.  count < N is AETH_E_LEN.  aeth_polar_mask sets the first
+ * K positions of that order to 1.  aeth_polar_create takes any mask: a caller with the 5G sequence, or a design for one
+ * SNR, passes their own.
+ *
+ * Refusals, each naming the value, before any device work: a null ctx, mask or out; n outside 3 .. 10
+ * (AETH_E_UNSUPPORTED); a mask byte above 1 (AETH_E_ARG, naming the index); K = 0; wrong lengths (AETH_E_LEN); unknown
+ * flag bits; ranges that share a byte; a misaligned flip_dev or rec_dev (AETH_E_ALIGN).  Getters return 0 for NULL and
+ * aeth_polar_destroy(NULL) is AETH_OK.  All device calls are ordered on the context's stream and none waits.
+ *
+ * Kernel.  aeth_polar_lanes lanes share a codeword (4, 8 or 16, chosen at create from n) and a workgroup is one wave of
+ * aeth_polar_group = 64 / lanes codewords on aeth_polar_lds_bytes of dynamic LDS.  Levels above `lanes` values are int16
+ * in LDS, those below live in registers and exchange across lanes; partial sums are packed bits; the tree walk is a
+ * schedule built at create, wholly frozen subtrees pruned.
+ *
+ * Not built: list decoding (SCL); rate-1 / SPC / repetition node shortcuts (they skip the leaf values the record
+ * needs); the 5G reliability sequence, sub-block interleaver and parity-check bits; systematic polar encoding; n > 10; an
+ * aeth_stream_op kind and host-slice flavours. */
+#define AETH_POLAR_CODEWORD 1u
+#define AETH_POLAR_NONE 0xFFFFFFFFu
+typedef struct aeth_polar_record { uint32_t index[4]; uint32_t abs[4]; } aeth_polar_record;
+AETH_API int aeth_polar_rank(uint32_t n, uint32_t *order_out, size_t count);
+AETH_API int aeth_polar_mask(uint32_t n, uint32_t K, uint8_t *mask_out, size_t count);
+AETH_API int aeth_polar_create(aeth_ctx *ctx, uint32_t n, const uint8_t *mask, aeth_polar **out);
+AETH_API int aeth_polar_destroy(aeth_polar *polar);
+AETH_API size_t aeth_polar_n(const aeth_polar *polar);
+AETH_API size_t aeth_polar_k(const aeth_polar *polar);
+AETH_API uint32_t aeth_polar_lanes(const aeth_polar *polar);       /* lanes per codeword */
+AETH_API uint32_t aeth_polar_group(const aeth_polar *polar);       /* codewords per decoder workgroup */
+AETH_API size_t aeth_polar_lds_bytes(const aeth_polar *polar);     /* dynamic LDS of a decoder workgroup */
+AETH_API int aeth_polar_encode(aeth_polar *polar, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded);
+AETH_API int aeth_polar_decode(aeth_polar *polar, const int8_t *soft_dev, size_t nsoft, const uint32_t *flip_dev, uint32_t flags,
+                               uint8_t *bits_dev, size_t nbits, aeth_polar_record *rec_dev);
 
 /* ---- OFDM symbols (no body in the reference: it has Fft, VecOps::vec_mul and chunks_mut(fft_len) framing only) ---- */
 /* The framing and the one-tap equaliser of an OFDM link; everything else such a link needs is above (aeth_seq_scramble,

@@ -30,6 +30,10 @@ pub const AETH_RS_PAYLOAD: u32 = 1;
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_rs_code { pub m: u32, pub poly: u32, pub fcr: u32, pub prim: u32, pub nroots: u32, pub n: u32 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_rs_record { pub corrected: u32, pub status: u32 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_rs_summary { pub n_failed: u64, pub n_corrected: u64 }
+#[repr(C)] pub struct aeth_polar { _p: [u8; 0] }
+pub const AETH_POLAR_CODEWORD: u32 = 1; pub const AETH_POLAR_NONE: u32 = 0xFFFF_FFFF;
+/// aeth_polar_record: the four information leaves with the least (|L|, i), ascending; empty slots hold 0xFFFFFFFF
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_polar_record { pub index: [u32; 4], pub abs: [u32; 4] }
 #[repr(C)] pub struct aeth_ofdm { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
@@ -405,6 +409,18 @@ extern "C" {
     pub fn aeth_rs_encode(rs: *mut aeth_rs, data_dev: *const u8, ndata: usize, depth: u32, coded_dev: *mut u8, ncoded: usize) -> c_int;
     pub fn aeth_rs_decode(rs: *mut aeth_rs, in_dev: *const u8, nin: usize, era_dev: *const u8, depth: u32, flags: u32, out_dev: *mut u8,
                           nout: usize, rec_dev: *mut aeth_rs_record, summary_dev: *mut aeth_rs_summary) -> c_int;
+    pub fn aeth_polar_rank(n: u32, order_out: *mut u32, count: usize) -> c_int;
+    pub fn aeth_polar_mask(n: u32, k: u32, mask_out: *mut u8, count: usize) -> c_int;
+    pub fn aeth_polar_create(ctx: *mut aeth_ctx, n: u32, mask: *const u8, out: *mut *mut aeth_polar) -> c_int;
+    pub fn aeth_polar_destroy(polar: *mut aeth_polar) -> c_int;
+    pub fn aeth_polar_n(polar: *const aeth_polar) -> usize;
+    pub fn aeth_polar_k(polar: *const aeth_polar) -> usize;
+    pub fn aeth_polar_lanes(polar: *const aeth_polar) -> u32;
+    pub fn aeth_polar_group(polar: *const aeth_polar) -> u32;
+    pub fn aeth_polar_lds_bytes(polar: *const aeth_polar) -> usize;
+    pub fn aeth_polar_encode(polar: *mut aeth_polar, bits_dev: *const u8, nbits: usize, coded_dev: *mut u8, ncoded: usize) -> c_int;
+    pub fn aeth_polar_decode(polar: *mut aeth_polar, soft_dev: *const i8, nsoft: usize, flip_dev: *const u32, flags: u32, bits_dev: *mut u8,
+                             nbits: usize, rec_dev: *mut aeth_polar_record) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;
