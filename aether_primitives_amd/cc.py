@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import Handle
 from ._lib import check
 from .modulation import DeviceBits, DeviceSoft
 
@@ -19,16 +20,17 @@ class _Code(C.Structure):
     _fields_ = [("k", C.c_uint32), ("n", C.c_uint32), ("poly", C.c_uint32 * 4)]
 
 
-class ConvCode:
+class ConvCode(Handle):
     """ConvCode(ctx, k, polys, block, warmup, traceback): output block D, warm-up A and traceback T in trellis steps
     (D + T <= 4096, A <= 4096).  `history` is A + T, the steps of soft values a continued `decode` wants in front."""
 
+    DESTROY = "aeth_cc_destroy"
+    NEEDS_CONTEXT = False                                            # the object holds nothing on the device
+
     def __init__(self, ctx, k, polys, block=512, warmup=64, traceback=64):
-        self.ctx = ctx
-        self._lib = _lib.load()
+        super().__init__(ctx)
         polys = [int(p) for p in polys]
         code = _Code(int(k), len(polys), (C.c_uint32 * 4)(*(polys + [0] * 4)[:4]))
-        self.h = C.c_void_p()
         check(self._lib.aeth_cc_create(ctx.h, C.byref(code), int(block), int(warmup), int(traceback), C.byref(self.h)))
         self.k, self.n, self.polys = int(k), len(polys), tuple(polys)
 
@@ -97,14 +99,3 @@ class ConvCode:
         if nbits:
             check(self._lib.aeth_copy_dev(self.ctx.h, C.c_void_p(out.ptr), C.c_void_p(full.ptr + T), nbits))
         return out
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self._lib.aeth_cc_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

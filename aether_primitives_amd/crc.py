@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import DeviceArray, Handle
 from ._lib import check
 from .modulation import DeviceBits
 
@@ -21,41 +22,20 @@ LANE_CHUNK = 16                                 # bytes a lane takes at a time o
 GROUP_TILE = 64 * LANE_CHUNK                    # bytes the largest group takes in one pass
 
 
-class DeviceU64:
+class DeviceU64(DeviceArray):
     """Device-resident `[u64]`: CRC registers and diff words."""
 
-    def __init__(self, ctx, n, host=None):
-        self.ctx, self.n = ctx, int(n)
-        self.ptr = ctx.alloc(max(self.n, 1) * 8)
-        if host is not None and self.n:
-            ctx.upload(self.ptr, np.ascontiguousarray(host, np.uint64))
-
-    def __len__(self):
-        return self.n
-
-    def to_host(self):
-        out = np.empty(self.n, np.uint64)
-        if self.n:
-            self.ctx.download(self.ptr, out)
-        return out
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr); self.ptr = None
-        except Exception:
-            pass
+    DTYPE = np.dtype(np.uint64)
 
 
-class CrcSummary:
+class CrcSummary(DeviceU64):
     """The two words of aeth_crc_summary on the device; `.to_host()` -> (n_bad, first_bad)."""
 
     def __init__(self, ctx):
-        self._w = DeviceU64(ctx, 2)
-        self.ptr = self._w.ptr
+        super().__init__(ctx, 2)
 
     def to_host(self):
-        n_bad, first_bad = self._w.to_host()
+        n_bad, first_bad = super().to_host()
         return int(n_bad), int(first_bad)
 
 
@@ -99,13 +79,13 @@ DeviceBits.pack_bits = pack_bits
 DeviceBits.unpack_bits = unpack_bits
 
 
-class Crc:
+class Crc(Handle):
     """Crc(ctx, r, poly, init=0, xorout=0): the object owns its weight table and the long route's scratch."""
 
+    DESTROY = "aeth_crc_destroy"
+
     def __init__(self, ctx, r, poly, init=0, xorout=0):
-        self.ctx = ctx
-        self._lib = _lib.load()
-        self.h = C.c_void_p()
+        super().__init__(ctx)
         check(self._lib.aeth_crc_create(ctx.h, int(r), int(poly), int(init), int(xorout), C.byref(self.h)))
         self.r, self.poly, self.init, self.xorout = int(r), int(poly), int(init), int(xorout)
 
@@ -163,15 +143,3 @@ class Crc:
         if summary == "host":
             s = s.to_host()
         return d, p, s
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            if self.ctx.h:                                           # a closed context has taken the stream with it
-                self._lib.aeth_crc_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -334,9 +334,7 @@ int aeth_cc_encode(aeth_cc *cc, const uint8_t *hist_bits_dev, const uint8_t *bit
                  nbits, n, nbits <= SIZE_MAX / n ? nbits * n : (size_t)0);
     if (nbits == 0) return AETH_OK;
     AETH_REQUIRE(bits_dev && coded_dev, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(bits_dev, nbits, coded_dev, ncoded) &&
-                     !aeth::ranges_touch(hist_bits_dev, cc->code.k - 1, coded_dev, ncoded),
-                 AETH_E_ARG, "the output overlaps an input");
+    if (int rc = aeth::check_disjoint({{bits_dev, nbits}, {hist_bits_dev, cc->code.k - 1}}, {{coded_dev, ncoded}})) return rc;
     const size_t blocks = (nbits + kBlock - 1) / kBlock;
     AETH_REQUIRE(blocks < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu bits need 2^31 workgroups or more", nbits);
     aeth::DeviceGuard dg(cc->ctx->device);
@@ -360,8 +358,7 @@ int aeth_cc_decode(aeth_cc *cc, const int8_t *hist_soft_dev, const int8_t *soft_
     if (nbits == 0) return AETH_OK;
     AETH_REQUIRE(soft_dev && bits_dev, AETH_E_ARG, "null pointer");
     const size_t nhist = ((size_t)cc->A + cc->T) * n;
-    AETH_REQUIRE(!aeth::ranges_touch(soft_dev, nsoft, bits_dev, nbits) && !aeth::ranges_touch(hist_soft_dev, nhist, bits_dev, nbits),
-                 AETH_E_ARG, "the output overlaps an input");
+    if (int rc = aeth::check_disjoint({{soft_dev, nsoft}, {hist_soft_dev, nhist}}, {{bits_dev, nbits}})) return rc;
     const size_t nfull = nbits / cc->D, tail = nbits % cc->D;
     const unsigned G = kWave >> (cc->code.k - 1);
     AETH_REQUIRE((nfull + G - 1) / G < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu bits in blocks of %u need 2^31 workgroups or more", nbits,

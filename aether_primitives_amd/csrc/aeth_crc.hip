@@ -377,8 +377,7 @@ int check_params(uint64_t r, uint64_t poly, uint64_t init, uint64_t xorout)
     return AETH_OK;
 }
 
-// a * b, or 2^64 - 1 where that does not fit
-uint64_t mul_sat(uint64_t a, uint64_t b) { return b && a > UINT64_MAX / b ? UINT64_MAX : a * b; }
+using aeth::mul_sat;
 
 }  // namespace
 
@@ -563,14 +562,9 @@ int aeth_crc_create(aeth_ctx *ctx, uint32_t r, uint64_t poly, uint64_t init, uin
 int aeth_crc_destroy(aeth_crc *crc)
 {
     if (!crc) return AETH_OK;
-    aeth::DeviceGuard dg(crc->ctx->device);
-    (void)hipStreamSynchronize(aeth::ctx_stream(crc->ctx));
-    const hipError_t e1 = aeth::scratch_release(crc->slab);
-    const hipError_t e2 = crc->tab_dev ? hipFree(crc->tab_dev) : hipSuccess;
+    const hipError_t freed = aeth::release_tables(crc->ctx, {crc->slab.p, crc->tab_dev});
     delete crc;
-    AETH_HIP(e1);
-    AETH_HIP(e2);
-    return AETH_OK;
+    return freed == hipSuccess ? AETH_OK : aeth::hip_fail(freed, "hipFree");
 }
 
 uint32_t aeth_crc_width(const aeth_crc *crc) { return crc ? crc->p.r : 0; }
@@ -594,8 +588,8 @@ int aeth_crc_exec(aeth_crc *crc, const uint8_t *bits_dev, size_t L, size_t F, co
     if (F == 0) return AETH_OK;
     AETH_REQUIRE(state_out_dev && (bits_dev || !n_in), AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned8(state_in_dev) && aeth::aligned8(state_out_dev), AETH_E_ALIGN, "state pointer not 8-byte aligned");
-    AETH_REQUIRE(!aeth::ranges_touch(state_out_dev, n_st, bits_dev, n_in) && !aeth::ranges_touch(state_out_dev, n_st, state_in_dev, n_st),
-                 AETH_E_ARG, "the output states overlap an input");
+    if (int rc = aeth::check_disjoint({{bits_dev, n_in}, {state_in_dev, n_st}}, {{state_out_dev, n_st}}, "the output states overlap an input"))
+        return rc;
     Plan pl{};
     pl.op = OP_EXEC; pl.in = bits_dev; pl.L = L; pl.F = F; pl.stride_in = L;
     pl.state_in = state_in_dev; pl.state_out = state_out_dev;
@@ -609,7 +603,7 @@ int aeth_crc_attach(aeth_crc *crc, const uint8_t *in_dev, size_t L, size_t F, ui
     AETH_REQUIRE(L < kMaxLen && n_out < kMaxLen, AETH_E_UNSUPPORTED, "%zu frames of %zu + %u bits: the output reaches 2^32 bytes", F, L, crc->p.r);
     if (F == 0) return AETH_OK;
     AETH_REQUIRE(out_dev && (in_dev || !n_in), AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(out_dev, n_out, in_dev, n_in), AETH_E_ARG, "the output overlaps the input");
+    if (int rc = aeth::check_disjoint({{in_dev, n_in}}, {{out_dev, n_out}})) return rc;
     Plan pl{};
     pl.op = OP_ATTACH; pl.in = in_dev; pl.L = L; pl.F = F; pl.stride_in = L; pl.out = out_dev;
     return run(crc, pl);
@@ -626,11 +620,8 @@ int aeth_crc_check(aeth_crc *crc, const uint8_t *in_dev, size_t L, size_t F, uin
     AETH_REQUIRE(n_diff < kMaxLen, AETH_E_UNSUPPORTED, "%zu frames: the diff words reach 2^32 bytes", F);
     AETH_REQUIRE(in_dev || !F, AETH_E_ARG, "in_dev is null");
     AETH_REQUIRE(aeth::aligned8(diff_dev) && aeth::aligned8(summary_dev), AETH_E_ALIGN, "diff_dev or summary_dev not 8-byte aligned");
-    const size_t n_sum = sizeof(aeth_crc_summary);
-    AETH_REQUIRE(!aeth::ranges_touch(diff_dev, n_diff, in_dev, n_in) && !aeth::ranges_touch(payload_dev, n_pay, in_dev, n_in) &&
-                 !aeth::ranges_touch(summary_dev, n_sum, in_dev, n_in), AETH_E_ARG, "an output overlaps the input");
-    AETH_REQUIRE(!aeth::ranges_touch(diff_dev, n_diff, payload_dev, n_pay) && !aeth::ranges_touch(diff_dev, n_diff, summary_dev, n_sum) &&
-                 !aeth::ranges_touch(payload_dev, n_pay, summary_dev, n_sum), AETH_E_ARG, "two outputs overlap");
+    if (int rc = aeth::check_disjoint({{in_dev, n_in}}, {{diff_dev, n_diff}, {payload_dev, n_pay}, {summary_dev, sizeof(aeth_crc_summary)}}))
+        return rc;
     if (F == 0 && !summary_dev) return AETH_OK;
     Plan pl{};
     pl.op = OP_CHECK; pl.in = in_dev; pl.L = L; pl.F = F; pl.stride_in = L + crc->p.r;
@@ -646,7 +637,7 @@ int aeth_bits_pack(aeth_ctx *ctx, const uint8_t *bits_dev, size_t nbits, int ord
     AETH_REQUIRE((uint64_t)nbits < kMaxLen, AETH_E_UNSUPPORTED, "nbits %zu: 2^32 or more in one call (cut at a multiple of 8)", nbits);
     if (nbits == 0) return AETH_OK;
     AETH_REQUIRE(bits_dev && bytes_dev, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(bytes_dev, nbytes, bits_dev, nbits), AETH_E_ARG, "the output overlaps the input");
+    if (int rc = aeth::check_disjoint({{bits_dev, nbits}}, {{bytes_dev, nbytes}})) return rc;
     aeth::DeviceGuard dg(ctx->device);
     const bool nt = aeth::streams_past_cache(nbits + nbytes);
     hipStream_t st = aeth::ctx_stream(ctx);
@@ -667,7 +658,7 @@ int aeth_bits_unpack(aeth_ctx *ctx, const uint8_t *bytes_dev, size_t nbytes, int
     AETH_REQUIRE((uint64_t)nbits < kMaxLen, AETH_E_UNSUPPORTED, "nbits %zu: 2^32 or more in one call (cut at a multiple of 8)", nbits);
     if (nbits == 0) return AETH_OK;
     AETH_REQUIRE(bits_dev && bytes_dev, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(bits_dev, nbits, bytes_dev, nbytes), AETH_E_ARG, "the output overlaps the input");
+    if (int rc = aeth::check_disjoint({{bytes_dev, nbytes}}, {{bits_dev, nbits}})) return rc;
     aeth::DeviceGuard dg(ctx->device);
     const bool nt = aeth::streams_past_cache(nbits + nbytes);
     hipStream_t st = aeth::ctx_stream(ctx);

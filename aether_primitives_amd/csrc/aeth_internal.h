@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include "../../include/aether_hip.h"
 #include "aeth_lane_hazards.h"
@@ -245,6 +246,56 @@ template <class T> int upload_table(aeth_ctx *ctx, const void *host, size_t byte
     return upload_table(ctx, host, bytes, (void **)dev, what);
 }
 
+// ---- the call frontier of the code modules: what a call checks between its handle and its first launch, one small step
+// each, run in the call's own order; none allocates
+inline uint64_t mul_sat(uint64_t a, uint64_t b) { return b && a > UINT64_MAX / b ? UINT64_MAX : a * b; }   // or 2^64 - 1
+inline int check_flags(uint32_t flags, uint32_t known)
+{
+    return flags & ~known ? set_error(AETH_E_ARG, "unknown flag bits 0x%x", flags & ~known) : AETH_OK;
+}
+// whole codewords on both sides, *F of them: an encoder's K bits in and N coded bits out, a decoder's (`dec`) N soft values
+// in and N or K bits out
+inline int check_codewords(bool dec, size_t nin, uint32_t per_in, size_t nout, uint32_t per_out, size_t *F)
+{
+    *F = nin / per_in;
+    AETH_REQUIRE(nin == *F * per_in, AETH_E_LEN, dec ? "nsoft %zu is no multiple of N = %u" : "nbits %zu is no multiple of K = %u", nin, per_in);
+    if (dec) AETH_REQUIRE(nout == *F * per_out, AETH_E_LEN, "%zu codewords give %zu bits (%u each), not %zu", *F, *F * per_out, per_out, nout);
+    else AETH_REQUIRE(nout / per_out == *F && nout % per_out == 0, AETH_E_LEN, "%zu codewords of N = %u are %llu coded bits, not %zu", *F,
+                      per_out, (unsigned long long)mul_sat(*F, per_out), nout);
+    return AETH_OK;
+}
+// No output may share a byte with an input or with another output: every output against every input, then every pair of
+// outputs.  The text follows the number of slots the call declares, not of those in use, unless the call words it (`io_text`).
+struct Span { const void *p; size_t bytes; };
+inline int check_disjoint(std::initializer_list<Span> in, std::initializer_list<Span> out, const char *io_text = nullptr)
+{
+    if (!io_text)
+        io_text = out.size() > 1 ? (in.size() > 1 ? "an output overlaps an input" : "an output overlaps the input")
+                                 : (in.size() > 1 ? "the output overlaps an input" : "the output overlaps the input");
+    for (const Span &o : out)
+        for (const Span &i : in) AETH_REQUIRE(!ranges_touch(o.p, o.bytes, i.p, i.bytes), AETH_E_ARG, "%s", io_text);
+    const char *oo_text = out.size() == 2 ? "the two outputs overlap" : "two outputs overlap";
+    for (const Span *a = out.begin(); a != out.end(); a++)
+        for (const Span *b = a + 1; b != out.end(); b++) AETH_REQUIRE(!ranges_touch(a->p, a->bytes, b->p, b->bytes), AETH_E_ARG, "%s", oo_text);
+    return AETH_OK;
+}
+// `count` of the caller's `noun` ("frames", "codewords") ask for `workgroups` of them in one launch
+inline int check_grid(uint64_t workgroups, size_t count, const char *noun)
+{
+    return workgroups >> 31 ? set_error(AETH_E_UNSUPPORTED, "%zu %s in one call: more than 2^31 workgroups", count, noun) : AETH_OK;
+}
+// a code object's destroy before it deletes the object, and its create when a later upload fails: waits for the context's
+// stream and frees each buffer that is there (the slab's first); the first HIP error comes back once all have been freed
+inline hipError_t release_tables(aeth_ctx *ctx, std::initializer_list<void *> bufs)
+{
+    DeviceGuard dg(ctx->device);
+    (void)hipStreamSynchronize(ctx_stream(ctx));
+    hipError_t first = hipSuccess;
+    for (void *b : bufs)
+        if (const hipError_t e = b ? hipFree(b) : hipSuccess; first == hipSuccess) first = e;
+    return first;
+}
+
 // What a call over complex samples checks behind its lengths and before any device work: n input samples, hist_elems
 // samples of history (hist may be null), n_out output elements of out_elem_bytes each, `count` of the caller's `noun`
 // ("frames", "outputs") on at most `grid` workgroups.
@@ -254,11 +305,9 @@ inline int check_buffers(const aeth_cf32 *hist, size_t hist_elems, const aeth_cf
     AETH_REQUIRE(in && out, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aligned8(in) && aligned8(hist), AETH_E_ALIGN, "input or history pointer not 8-byte aligned");
     AETH_REQUIRE(((uintptr_t)out & (out_elem_bytes - 1)) == 0, AETH_E_ALIGN, "output pointer not %zu-byte aligned", out_elem_bytes);
-    AETH_REQUIRE(!ranges_touch(out, n_out * out_elem_bytes, in, n * sizeof(aeth_cf32)) &&
-                 !ranges_touch(out, n_out * out_elem_bytes, hist, hist_elems * sizeof(aeth_cf32)), AETH_E_ARG,
-                 "the output range overlaps the input (or its history)");
-    AETH_REQUIRE(grid < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu %s in one call: more than 2^31 workgroups", count, noun);
-    return AETH_OK;
+    const int rc = check_disjoint({{in, n * sizeof(aeth_cf32)}, {hist, hist_elems * sizeof(aeth_cf32)}}, {{out, n_out * out_elem_bytes}},
+                                  "the output range overlaps the input (or its history)");
+    return rc ? rc : check_grid(grid, count, noun);
 }
 }  // namespace aeth
 

@@ -231,8 +231,6 @@ uint32_t group_of(uint32_t z, uint64_t state)
     return (uint32_t)std::max<uint64_t>(1, std::min(by_lanes, by_lds));
 }
 
-uint64_t mul_sat(uint64_t a, uint64_t b) { return b && a > UINT64_MAX / b ? UINT64_MAX : a * b; }
-
 }  // namespace
 
 struct aeth_ldpc {
@@ -288,7 +286,7 @@ int aeth_ldpc_create(aeth_ctx *ctx, const aeth_ldpc_code *code, aeth_ldpc **out)
     rc = aeth::upload_table(ctx, tab.data(), tab.size() * sizeof(uint32_t), &l->tab_dev, "aeth_ldpc_create: edge table");
     if (!rc) rc = aeth::upload_table(ctx, Pt.data(), Pt.size() * sizeof(uint64_t), &l->pt_dev, "aeth_ldpc_create: generator");
     if (rc) {
-        if (l->tab_dev) (void)hipFree(l->tab_dev);
+        (void)aeth::release_tables(ctx, {l->tab_dev, l->pt_dev});
         delete l;
         return rc;
     }
@@ -299,14 +297,9 @@ int aeth_ldpc_create(aeth_ctx *ctx, const aeth_ldpc_code *code, aeth_ldpc **out)
 int aeth_ldpc_destroy(aeth_ldpc *l)
 {
     if (!l) return AETH_OK;
-    aeth::DeviceGuard dg(l->ctx->device);
-    (void)hipStreamSynchronize(aeth::ctx_stream(l->ctx));
-    const hipError_t e1 = l->tab_dev ? hipFree(l->tab_dev) : hipSuccess;
-    const hipError_t e2 = l->pt_dev ? hipFree(l->pt_dev) : hipSuccess;
+    const hipError_t freed = aeth::release_tables(l->ctx, {l->tab_dev, l->pt_dev});
     delete l;
-    AETH_HIP(e1);
-    AETH_HIP(e2);
-    return AETH_OK;
+    return freed == hipSuccess ? AETH_OK : aeth::hip_fail(freed, "hipFree");
 }
 
 size_t aeth_ldpc_n(const aeth_ldpc *l) { return l ? l->N : 0; }
@@ -321,15 +314,13 @@ uint32_t aeth_ldpc_group(const aeth_ldpc *l) { return l ? l->G : 0; }
 int aeth_ldpc_encode(aeth_ldpc *l, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded)
 {
     AETH_REQUIRE(l, AETH_E_ARG, "ldpc is null");
-    const size_t F = nbits / l->K;
-    AETH_REQUIRE(nbits == F * l->K, AETH_E_LEN, "nbits %zu is no multiple of K = %u", nbits, l->K);
-    AETH_REQUIRE(ncoded / l->N == F && ncoded % l->N == 0, AETH_E_LEN, "%zu codewords of N = %u are %llu coded bits, not %zu", F, l->N,
-                 (unsigned long long)mul_sat(F, l->N), ncoded);
+    size_t F;
+    if (int rc = aeth::check_codewords(false, nbits, l->K, ncoded, l->N, &F)) return rc;
     if (F == 0) return AETH_OK;
     AETH_REQUIRE(bits_dev && coded_dev, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(coded_dev, ncoded, bits_dev, nbits), AETH_E_ARG, "the output overlaps the input");
+    if (int rc = aeth::check_disjoint({{bits_dev, nbits}}, {{coded_dev, ncoded}})) return rc;
     const uint64_t wgs = (F + kEncGroup - 1) / kEncGroup;
-    AETH_REQUIRE(wgs < ((uint64_t)1 << 31), AETH_E_UNSUPPORTED, "%zu codewords in one call: more than 2^31 workgroups", F);
+    if (int rc = aeth::check_grid(wgs, F, "codewords")) return rc;
     aeth::DeviceGuard dg(l->ctx->device);
     hipStream_t st = aeth::ctx_stream(l->ctx);
     EncCall a{bits_dev, coded_dev, l->pt_dev, (uint64_t)F, l->N, l->K, l->M, l->KW};
@@ -342,21 +333,17 @@ int aeth_ldpc_decode(aeth_ldpc *l, const int8_t *soft_dev, size_t nsoft, uint32_
                      aeth_ldpc_record *rec_dev)
 {
     AETH_REQUIRE(l, AETH_E_ARG, "ldpc is null");
-    AETH_REQUIRE(!(flags & ~(uint32_t)(AETH_LDPC_EARLY | AETH_LDPC_PAYLOAD)), AETH_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)(AETH_LDPC_EARLY | AETH_LDPC_PAYLOAD));
+    if (int rc = aeth::check_flags(flags, AETH_LDPC_EARLY | AETH_LDPC_PAYLOAD)) return rc;
     AETH_REQUIRE(max_iter <= kMaxIter, AETH_E_ARG, "max_iter %u above %u", max_iter, kMaxIter);
-    const size_t F = nsoft / l->N;
     const uint32_t nb = (flags & AETH_LDPC_PAYLOAD) ? l->K : l->N;
-    AETH_REQUIRE(nsoft == F * l->N, AETH_E_LEN, "nsoft %zu is no multiple of N = %u", nsoft, l->N);
-    AETH_REQUIRE(nbits == F * nb, AETH_E_LEN, "%zu codewords give %zu bits (%u each), not %zu", F, F * nb, nb, nbits);
+    size_t F;
+    if (int rc = aeth::check_codewords(true, nsoft, l->N, nbits, nb, &F)) return rc;
     if (F == 0) return AETH_OK;
     AETH_REQUIRE(soft_dev && bits_dev, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned4(rec_dev), AETH_E_ALIGN, "rec_dev not 4-byte aligned");
-    const size_t nrec = F * sizeof(aeth_ldpc_record);
-    AETH_REQUIRE(!aeth::ranges_touch(bits_dev, nbits, soft_dev, nsoft) && !aeth::ranges_touch(rec_dev, nrec, soft_dev, nsoft), AETH_E_ARG,
-                 "an output overlaps the input");
-    AETH_REQUIRE(!aeth::ranges_touch(rec_dev, nrec, bits_dev, nbits), AETH_E_ARG, "the two outputs overlap");
+    if (int rc = aeth::check_disjoint({{soft_dev, nsoft}}, {{bits_dev, nbits}, {rec_dev, F * sizeof(aeth_ldpc_record)}})) return rc;
     const uint64_t wgs = (F + l->G - 1) / l->G;
-    AETH_REQUIRE(wgs < ((uint64_t)1 << 31), AETH_E_UNSUPPORTED, "%zu codewords in one call: more than 2^31 workgroups", F);
+    if (int rc = aeth::check_grid(wgs, F, "codewords")) return rc;
     aeth::DeviceGuard dg(l->ctx->device);
     hipStream_t st = aeth::ctx_stream(l->ctx);
     const size_t lds = dec_lds(l);

@@ -446,7 +446,7 @@ int aeth_demod_soft(aeth_ctx *ctx, const aeth_cf32 *sym, size_t nsym, int bps, c
     if (nsym == 0) return AETH_OK;
     AETH_REQUIRE(sym && out, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned8(sym), AETH_E_ALIGN, "pointer alignment");
-    AETH_REQUIRE(!aeth::ranges_touch(sym, nsym * sizeof(float2), out, nout), AETH_E_ARG, "the output overlaps the symbols");
+    if (int rc = aeth::check_disjoint({{sym, nsym * sizeof(float2)}}, {{out, nout}}, "the output overlaps the symbols")) return rc;
     AETH_REQUIRE((nsym + kBlock - 1) / kBlock < ((size_t)1 << 31), AETH_E_UNSUPPORTED, "%zu symbols need 2^31 workgroups or more", nsym);
     aeth::DeviceGuard dg(ctx->device);
     const bool nt = aeth::streams_past_cache(nsym * sizeof(float2));

@@ -263,8 +263,6 @@ uint32_t stride_of(uint32_t n, uint32_t T)
     return raw + ((2 * T + 128 - raw % 128) % 128);
 }
 
-uint64_t mul_sat(uint64_t a, uint64_t b) { return b && a > UINT64_MAX / b ? UINT64_MAX : a * b; }
-
 }  // namespace
 
 struct aeth_polar {
@@ -334,7 +332,7 @@ int aeth_polar_create(aeth_ctx *ctx, uint32_t n, const uint8_t *mask, aeth_polar
     rc = aeth::upload_table(ctx, sched.data(), sched.size() * sizeof(uint32_t), &p->sched_dev, "aeth_polar_create: schedule");
     if (!rc) rc = aeth::upload_table(ctx, tab.data(), tab.size() * sizeof(uint16_t), &p->pos_dev, "aeth_polar_create: position table");
     if (rc) {
-        if (p->sched_dev) (void)hipFree(p->sched_dev);
+        (void)aeth::release_tables(ctx, {p->sched_dev, p->pos_dev});
         delete p;
         return rc;
     }
@@ -345,14 +343,9 @@ int aeth_polar_create(aeth_ctx *ctx, uint32_t n, const uint8_t *mask, aeth_polar
 int aeth_polar_destroy(aeth_polar *p)
 {
     if (!p) return AETH_OK;
-    aeth::DeviceGuard dg(p->ctx->device);
-    (void)hipStreamSynchronize(aeth::ctx_stream(p->ctx));
-    const hipError_t e1 = p->sched_dev ? hipFree(p->sched_dev) : hipSuccess;
-    const hipError_t e2 = p->pos_dev ? hipFree(p->pos_dev) : hipSuccess;
+    const hipError_t freed = aeth::release_tables(p->ctx, {p->sched_dev, p->pos_dev});
     delete p;
-    AETH_HIP(e1);
-    AETH_HIP(e2);
-    return AETH_OK;
+    return freed == hipSuccess ? AETH_OK : aeth::hip_fail(freed, "hipFree");
 }
 
 size_t aeth_polar_n(const aeth_polar *p) { return p ? p->N : 0; }
@@ -364,16 +357,14 @@ size_t aeth_polar_lds_bytes(const aeth_polar *p) { return p ? (size_t)p->G * p->
 int aeth_polar_encode(aeth_polar *p, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded)
 {
     AETH_REQUIRE(p, AETH_E_ARG, "polar is null");
-    const size_t F = nbits / p->K;
-    AETH_REQUIRE(nbits == F * p->K, AETH_E_LEN, "nbits %zu is no multiple of K = %u", nbits, p->K);
-    AETH_REQUIRE(ncoded / p->N == F && ncoded % p->N == 0, AETH_E_LEN, "%zu codewords of N = %u are %llu coded bits, not %zu", F, p->N,
-                 (unsigned long long)mul_sat(F, p->N), ncoded);
+    size_t F;
+    if (int rc = aeth::check_codewords(false, nbits, p->K, ncoded, p->N, &F)) return rc;
     if (F == 0) return AETH_OK;
     AETH_REQUIRE(bits_dev && coded_dev, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(coded_dev, ncoded, bits_dev, nbits), AETH_E_ARG, "the output overlaps the input");
+    if (int rc = aeth::check_disjoint({{bits_dev, nbits}}, {{coded_dev, ncoded}})) return rc;
     const uint64_t tiles = ((uint64_t)ncoded + kTileBits - 1) / kTileBits;
     const uint64_t wgs = (tiles + kEncBlock / kWave - 1) / (kEncBlock / kWave);
-    AETH_REQUIRE(wgs < ((uint64_t)1 << 31), AETH_E_UNSUPPORTED, "%zu codewords in one call: more than 2^31 workgroups", F);
+    if (int rc = aeth::check_grid(wgs, F, "codewords")) return rc;
     aeth::DeviceGuard dg(p->ctx->device);
     hipStream_t st = aeth::ctx_stream(p->ctx);
     EncCall a{bits_dev, coded_dev, p->pos_dev, (uint64_t)ncoded, p->n, p->K};
@@ -386,22 +377,17 @@ int aeth_polar_decode(aeth_polar *p, const int8_t *soft_dev, size_t nsoft, const
                       size_t nbits, aeth_polar_record *rec_dev)
 {
     AETH_REQUIRE(p, AETH_E_ARG, "polar is null");
-    AETH_REQUIRE(!(flags & ~(uint32_t)AETH_POLAR_CODEWORD), AETH_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)AETH_POLAR_CODEWORD);
-    const size_t F = nsoft / p->N;
-    const uint32_t nb = (flags & AETH_POLAR_CODEWORD) ? p->N : p->K;
-    AETH_REQUIRE(nsoft == F * p->N, AETH_E_LEN, "nsoft %zu is no multiple of N = %u", nsoft, p->N);
-    AETH_REQUIRE(nbits == F * nb, AETH_E_LEN, "%zu codewords give %zu bits (%u each), not %zu", F, F * nb, nb, nbits);
+    if (int rc = aeth::check_flags(flags, AETH_POLAR_CODEWORD)) return rc;
+    size_t F;
+    if (int rc = aeth::check_codewords(true, nsoft, p->N, nbits, (flags & AETH_POLAR_CODEWORD) ? p->N : p->K, &F)) return rc;
     if (F == 0) return AETH_OK;
     AETH_REQUIRE(soft_dev && bits_dev, AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned4(flip_dev), AETH_E_ALIGN, "flip_dev not 4-byte aligned");
     AETH_REQUIRE(aeth::aligned4(rec_dev), AETH_E_ALIGN, "rec_dev not 4-byte aligned");
     const size_t nrec = F * sizeof(aeth_polar_record), nflip = F * sizeof(uint32_t);
-    AETH_REQUIRE(!aeth::ranges_touch(bits_dev, nbits, soft_dev, nsoft) && !aeth::ranges_touch(rec_dev, nrec, soft_dev, nsoft) &&
-                 !aeth::ranges_touch(bits_dev, nbits, flip_dev, nflip) && !aeth::ranges_touch(rec_dev, nrec, flip_dev, nflip), AETH_E_ARG,
-                 "an output overlaps an input");
-    AETH_REQUIRE(!aeth::ranges_touch(rec_dev, nrec, bits_dev, nbits), AETH_E_ARG, "the two outputs overlap");
+    if (int rc = aeth::check_disjoint({{soft_dev, nsoft}, {flip_dev, nflip}}, {{bits_dev, nbits}, {rec_dev, nrec}})) return rc;
     const uint64_t wgs = (F + p->G - 1) / p->G;
-    AETH_REQUIRE(wgs < ((uint64_t)1 << 31), AETH_E_UNSUPPORTED, "%zu codewords in one call: more than 2^31 workgroups", F);
+    if (int rc = aeth::check_grid(wgs, F, "codewords")) return rc;
     aeth::DeviceGuard dg(p->ctx->device);
     hipStream_t st = aeth::ctx_stream(p->ctx);
     DecCall a{};

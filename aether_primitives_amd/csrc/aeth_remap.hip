@@ -254,15 +254,9 @@ int aeth_remap_create(aeth_ctx *ctx, const int32_t *map, size_t r_out, size_t r_
 int aeth_remap_destroy(aeth_remap *rm)
 {
     if (!rm) return AETH_OK;
-    hipError_t e = hipSuccess;
-    if (rm->tab_dev) {
-        aeth::DeviceGuard dg(rm->ctx->device);
-        (void)hipStreamSynchronize(aeth::ctx_stream(rm->ctx));
-        e = hipFree(rm->tab_dev);
-    }
+    const hipError_t freed = aeth::release_tables(rm->ctx, {rm->tab_dev});
     delete rm;
-    AETH_HIP(e);
-    return AETH_OK;
+    return freed == hipSuccess ? AETH_OK : aeth::hip_fail(freed, "hipFree");
 }
 
 size_t aeth_remap_in_period(const aeth_remap *rm) { return rm ? rm->r_in : 0; }
@@ -287,7 +281,7 @@ int aeth_remap_exec(aeth_remap *rm, const void *in_dev, size_t n_in, void *out_d
     AETH_REQUIRE(n_in >= need, AETH_E_LEN, "input holds %zu bytes, %zu outputs read %zu", n_in, n_out, need);
     if (n_out == 0) return AETH_OK;
     AETH_REQUIRE(out_dev && (in_dev || need == 0), AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(in_dev, n_in, out_dev, n_out), AETH_E_ARG, "the output overlaps the input");
+    if (int rc = aeth::check_disjoint({{in_dev, n_in}}, {{out_dev, n_out}})) return rc;
     aeth::DeviceGuard dg(rm->ctx->device);
     const bool nt = aeth::streams_past_cache(need + n_out);
     hipStream_t st = aeth::ctx_stream(rm->ctx);

@@ -230,8 +230,6 @@ __global__ __launch_bounds__(kBlock) void rs_summary_kernel(const Sum *sums, siz
     if (threadIdx.x == 0) *out = t;
 }
 
-uint64_t mul_sat(uint64_t a, uint64_t b) { return b && a > UINT64_MAX / b ? UINT64_MAX : a * b; }
-
 // every rule of the header on a code; fills the field
 int check_code(const aeth_rs_code *code, rc::Field &f)
 {
@@ -262,7 +260,7 @@ int check_frames(const char *in_name, size_t nin, size_t in_frame, const char *o
     AETH_REQUIRE(nin % in_frame == 0, AETH_E_LEN, "%s %zu is no multiple of the frame of %zu bytes", in_name, nin, in_frame);
     *F = nin / in_frame;
     AETH_REQUIRE(nout / out_frame == *F && nout % out_frame == 0, AETH_E_LEN, "%zu frames are %llu bytes of %s (%zu each), not %zu", *F,
-                 (unsigned long long)mul_sat(*F, out_frame), out_name, out_frame, nout);
+                 (unsigned long long)aeth::mul_sat(*F, out_frame), out_name, out_frame, nout);
     return AETH_OK;
 }
 
@@ -341,7 +339,7 @@ int aeth_rs_host_encode(const aeth_rs_code *code, const uint8_t *data_host, size
     if (rv) return rv;
     if (F == 0) return AETH_OK;
     AETH_REQUIRE(data_host && coded_host, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(coded_host, ncoded, data_host, ndata), AETH_E_ARG, "the output overlaps the input");
+    if ((rv = aeth::check_disjoint({{data_host, ndata}}, {{coded_host, ncoded}}))) return rv;
     const rc::Tab t = rc::tab_of(f, code_of(code));
     uint8_t g[rc::kMaxRoots + 1];
     rc::generator(t, g);
@@ -362,14 +360,13 @@ int aeth_rs_host_decode(const aeth_rs_code *code, const uint8_t *in_host, size_t
     if (rv) return rv;
     rv = check_depth(depth);
     if (rv) return rv;
-    AETH_REQUIRE(!(flags & ~(uint32_t)AETH_RS_PAYLOAD), AETH_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)AETH_RS_PAYLOAD);
+    if ((rv = aeth::check_flags(flags, AETH_RS_PAYLOAD))) return rv;
     const uint32_t nb = (flags & AETH_RS_PAYLOAD) ? code->n - code->nroots : code->n;
     size_t F;
     rv = check_frames("nin", nin, (size_t)depth * code->n, "output", nout, (size_t)depth * nb, &F);
     if (rv) return rv;
     AETH_REQUIRE(!F || (in_host && out_host), AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(out_host, nout, in_host, nin) && !aeth::ranges_touch(out_host, nout, era_host, nin), AETH_E_ARG,
-                 "the output overlaps an input");
+    if ((rv = aeth::check_disjoint({{in_host, nin}, {era_host, nin}}, {{out_host, nout}}))) return rv;
     const rc::Tab t = rc::tab_of(f, code_of(code));
     aeth_rs_summary sum{0, 0};
     for (size_t fr = 0; fr < F; fr++)
@@ -417,14 +414,9 @@ int aeth_rs_create(aeth_ctx *ctx, const aeth_rs_code *code, aeth_rs **out)
 int aeth_rs_destroy(aeth_rs *rs)
 {
     if (!rs) return AETH_OK;
-    aeth::DeviceGuard dg(rs->ctx->device);
-    (void)hipStreamSynchronize(aeth::ctx_stream(rs->ctx));
-    const hipError_t e1 = aeth::scratch_release(rs->slab);
-    const hipError_t e2 = rs->tab_dev ? hipFree(rs->tab_dev) : hipSuccess;
+    const hipError_t freed = aeth::release_tables(rs->ctx, {rs->slab.p, rs->tab_dev});
     delete rs;
-    AETH_HIP(e1);
-    AETH_HIP(e2);
-    return AETH_OK;
+    return freed == hipSuccess ? AETH_OK : aeth::hip_fail(freed, "hipFree");
 }
 
 size_t aeth_rs_n(const aeth_rs *rs) { return rs ? rs->c.n : 0; }
@@ -445,11 +437,11 @@ int aeth_rs_encode(aeth_rs *rs, const uint8_t *data_dev, size_t ndata, uint32_t 
     if (rv) return rv;
     if (F == 0) return AETH_OK;
     AETH_REQUIRE(data_dev && coded_dev, AETH_E_ARG, "null pointer");
-    AETH_REQUIRE(!aeth::ranges_touch(coded_dev, ncoded, data_dev, ndata), AETH_E_ARG, "the output overlaps the input");
+    if ((rv = aeth::check_disjoint({{data_dev, ndata}}, {{coded_dev, ncoded}}))) return rv;
     const Geom g = geom_of(rs, F, depth);
     const uint32_t G = (uint32_t)kBlock >> rs->lg;
     const uint64_t wgs = (g.W + G - 1) / G;
-    AETH_REQUIRE(wgs < ((uint64_t)1 << 31), AETH_E_UNSUPPORTED, "%zu frames in one call: more than 2^31 workgroups", F);
+    if ((rv = aeth::check_grid(wgs, F, "frames"))) return rv;
     aeth::DeviceGuard dg(rs->ctx->device);
     hipStream_t st = aeth::ctx_stream(rs->ctx);
     EncCall a{g, data_dev, coded_dev, rs->tab_dev + 832};
@@ -464,7 +456,7 @@ int aeth_rs_decode(aeth_rs *rs, const uint8_t *in_dev, size_t nin, const uint8_t
     AETH_REQUIRE(rs, AETH_E_ARG, "rs is null");
     int rv = check_depth(depth);
     if (rv) return rv;
-    AETH_REQUIRE(!(flags & ~(uint32_t)AETH_RS_PAYLOAD), AETH_E_ARG, "unknown flag bits 0x%x", flags & ~(uint32_t)AETH_RS_PAYLOAD);
+    if ((rv = aeth::check_flags(flags, AETH_RS_PAYLOAD))) return rv;
     const uint32_t nb = (flags & AETH_RS_PAYLOAD) ? rs->c.n - rs->c.nroots : rs->c.n;
     size_t F;
     rv = check_frames("nin", nin, (size_t)depth * rs->c.n, "output", nout, (size_t)depth * nb, &F);
@@ -472,18 +464,14 @@ int aeth_rs_decode(aeth_rs *rs, const uint8_t *in_dev, size_t nin, const uint8_t
     AETH_REQUIRE(!F || (in_dev && out_dev), AETH_E_ARG, "null pointer");
     AETH_REQUIRE(aeth::aligned4(rec_dev), AETH_E_ALIGN, "rec_dev not 4-byte aligned");
     AETH_REQUIRE(aeth::aligned8(summary_dev), AETH_E_ALIGN, "summary_dev not 8-byte aligned");
-    const size_t nrec = mul_sat(mul_sat(F, depth), sizeof(aeth_rs_record)), nsum = sizeof(aeth_rs_summary);
-    AETH_REQUIRE(!aeth::ranges_touch(out_dev, nout, in_dev, nin) && !aeth::ranges_touch(out_dev, nout, era_dev, nin) &&
-                 !aeth::ranges_touch(rec_dev, nrec, in_dev, nin) && !aeth::ranges_touch(rec_dev, nrec, era_dev, nin) &&
-                 !aeth::ranges_touch(summary_dev, nsum, in_dev, nin) && !aeth::ranges_touch(summary_dev, nsum, era_dev, nin), AETH_E_ARG,
-                 "an output overlaps an input");
-    AETH_REQUIRE(!aeth::ranges_touch(rec_dev, nrec, out_dev, nout) && !aeth::ranges_touch(summary_dev, nsum, out_dev, nout) &&
-                 !aeth::ranges_touch(summary_dev, nsum, rec_dev, nrec), AETH_E_ARG, "two outputs overlap");
+    const size_t nrec = aeth::mul_sat(aeth::mul_sat(F, depth), sizeof(aeth_rs_record));
+    rv = aeth::check_disjoint({{in_dev, nin}, {era_dev, nin}}, {{out_dev, nout}, {rec_dev, nrec}, {summary_dev, sizeof(aeth_rs_summary)}});
+    if (rv) return rv;
     if (F == 0 && !summary_dev) return AETH_OK;
     const Geom g = geom_of(rs, F, depth);
     const uint32_t G = (uint32_t)kBlock >> rs->lg;
     const uint64_t wgs = (g.W + G - 1) / G;
-    AETH_REQUIRE(wgs < ((uint64_t)1 << 31), AETH_E_UNSUPPORTED, "%zu frames in one call: more than 2^31 workgroups", F);
+    if ((rv = aeth::check_grid(wgs, F, "frames"))) return rv;
     aeth::DeviceGuard dg(rs->ctx->device);
     Sum *sums = nullptr;
     if (summary_dev && wgs) {

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import DeviceArray, Handle
 from ._lib import check
 from .modulation import DeviceBits, DeviceSoft
 
@@ -60,37 +61,19 @@ def staircase(rows, cols, z, col_weight=3, seed=0):
     return shift
 
 
-class DeviceRecords:
+class DeviceRecords(DeviceArray):
     """Device-resident `[aeth_ldpc_record]`; `.to_host()` -> structured array with `iterations` and `unsatisfied`."""
 
-    def __init__(self, ctx, n):
-        self.ctx, self.n = ctx, int(n)
-        self.ptr = ctx.alloc(max(self.n, 1) * 8)
-
-    def __len__(self):
-        return self.n
-
-    def to_host(self):
-        out = np.zeros(self.n, RECORD)
-        if self.n:
-            self.ctx.download(self.ptr, out.view(np.uint8))
-        return out
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr); self.ptr = None
-        except Exception:
-            pass
+    DTYPE = RECORD
 
 
-class Ldpc:
+class Ldpc(Handle):
     """Ldpc(ctx, shift, z): the object owns the generator P and the shift table on the device."""
 
+    DESTROY = "aeth_ldpc_destroy"
+
     def __init__(self, ctx, shift, z):
-        self.ctx = ctx
-        self._lib = _lib.load()
-        self.h = C.c_void_p()
+        super().__init__(ctx)
         code, tab = _code(shift, z)
         check(self._lib.aeth_ldpc_create(ctx.h, C.byref(code), C.byref(self.h)))
         self.shift = tab.copy()
@@ -126,15 +109,3 @@ class Ldpc:
         check(self._lib.aeth_ldpc_decode(self.h, C.c_void_p(soft.ptr), soft.n, int(max_iter), flags, C.c_void_p(out.ptr), out.n,
                                          C.c_void_p(rec.ptr) if rec is not None else None))
         return out, rec
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            if self.ctx.h:                                           # a closed context has taken the stream with it
-                self._lib.aeth_ldpc_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

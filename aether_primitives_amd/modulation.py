@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import DeviceArray
 from ._lib import check
 from .context import DeviceVec
 
@@ -12,50 +13,16 @@ GENERIC_BPSK_TABLE = np.array([1 + 1j, -1 - 1j], np.complex64)                  
 GENERIC_QPSK_TABLE = np.array([1 + 1j, -1 + 1j, 1 - 1j, -1 - 1j], np.complex64)   # modulation.rs:87-92
 
 
-class DeviceBits:
+class DeviceBits(DeviceArray):
     """u8-per-bit buffer in HBM."""
 
-    def __init__(self, ctx, n, host=None):
-        self.ctx, self.n = ctx, int(n)
-        self.ptr = ctx.alloc(max(self.n, 1))
-        if host is not None:
-            ctx.upload(self.ptr, np.ascontiguousarray(host, np.uint8))
-
-    def to_host(self):
-        out = np.empty(self.n, np.uint8)
-        if self.n:
-            self.ctx.download(self.ptr, out)
-        return out
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr); self.ptr = None
-        except Exception:
-            pass
+    DTYPE = np.dtype(np.uint8)
 
 
-class DeviceSoft:
+class DeviceSoft(DeviceArray):
     """int8 soft decisions in HBM, one per coded bit: positive means bit 0 is likelier, 0 is an erasure."""
 
-    def __init__(self, ctx, n, host=None):
-        self.ctx, self.n = ctx, int(n)
-        self.ptr = ctx.alloc(max(self.n, 1))
-        if host is not None and self.n:
-            ctx.upload(self.ptr, np.ascontiguousarray(host, np.int8))
-
-    def to_host(self):
-        out = np.empty(self.n, np.int8)
-        if self.n:
-            self.ctx.download(self.ptr, out)
-        return out
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr); self.ptr = None
-        except Exception:
-            pass
+    DTYPE = np.dtype(np.int8)
 
 
 class _Modulation:

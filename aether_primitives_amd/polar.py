@@ -13,8 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import DeviceArray, Handle
 from ._lib import check
-from ._records import DeviceRecordArray
 from .modulation import DeviceBits, DeviceSoft
 
 CODEWORD = 1                                    # AETH_POLAR_CODEWORD
@@ -38,39 +38,25 @@ def mask(n, K):
     return out
 
 
-class DeviceRecords(DeviceRecordArray):
+class DeviceRecords(DeviceArray):
     """Device-resident `[aeth_polar_record]`; `.to_host()` -> structured array with `index` and `abs`, four each."""
 
     DTYPE = RECORD
 
 
-class DeviceFlips:
+class DeviceFlips(DeviceArray):
     """Device-resident `[u32]`: one flip position per codeword."""
 
-    def __init__(self, ctx, n, host=None):
-        self.ctx, self.n = ctx, int(n)
-        self.ptr = ctx.alloc(max(self.n, 1) * 4)
-        if host is not None and self.n:
-            ctx.upload(self.ptr, np.ascontiguousarray(host, np.uint32))
-
-    def __len__(self):
-        return self.n
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr); self.ptr = None
-        except Exception:
-            pass
+    DTYPE = np.dtype(np.uint32)
 
 
-class Polar:
+class Polar(Handle):
     """Polar(ctx, n, mask): the object owns the decoder's schedule and the position tables on the device."""
 
+    DESTROY = "aeth_polar_destroy"
+
     def __init__(self, ctx, n, mask):
-        self.ctx = ctx
-        self._lib = _lib.load()
-        self.h = C.c_void_p()
+        super().__init__(ctx)
         m = np.ascontiguousarray(mask, np.uint8)
         assert m.size == (1 << n if MIN_N <= n <= MAX_N else m.size), "the mask holds 2^n bytes"
         check(self._lib.aeth_polar_create(ctx.h, int(n), m.ctypes.data_as(C.c_void_p), C.byref(self.h)))
@@ -107,15 +93,3 @@ class Polar:
         check(self._lib.aeth_polar_decode(self.h, C.c_void_p(soft.ptr), soft.n, C.c_void_p(flip.ptr) if flip is not None else None,
                                           CODEWORD if codeword else 0, C.c_void_p(out.ptr), out.n, rec._p() if rec is not None else None))
         return out, rec
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            if self.ctx.h:                                           # a closed context has taken the stream with it
-                self._lib.aeth_polar_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

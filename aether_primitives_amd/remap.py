@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import Handle
 from ._lib import check
 from .modulation import DeviceBits, DeviceSoft
 
@@ -70,15 +71,15 @@ def bicm16_map(n_cbps, n_bpsc):
     return out, int(n_cbps)
 
 
-class Remap:
+class Remap(Handle):
     """Remap(ctx, map, r_in): the object owns the device copy of its table."""
 
+    DESTROY = "aeth_remap_destroy"
+
     def __init__(self, ctx, map, r_in):
-        self.ctx = ctx
-        self._lib = _lib.load()
+        super().__init__(ctx)
         self.map = _i32(map).copy()
         self.r_in = int(r_in)
-        self.h = C.c_void_p()
         check(self._lib.aeth_remap_create(ctx.h, _p(self.map), self.map.size, self.r_in, C.byref(self.h)))
 
     @classmethod
@@ -136,15 +137,3 @@ class Remap:
             out = type(x)(self.ctx, self.out_count(x.n) if n_out is None else int(n_out))
         check(self._lib.aeth_remap_exec(self.h, C.c_void_p(x.ptr), x.n, C.c_void_p(out.ptr), out.n, int(fill) & 0xff))
         return out
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            if self.ctx.h:                                           # a closed context has taken the stream with it
-                self._lib.aeth_remap_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

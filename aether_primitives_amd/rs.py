@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._device import DeviceArray, Handle
 from ._lib import check
 from .modulation import DeviceBits
 
@@ -82,57 +83,31 @@ def host_decode(code, coded, erasures=None, depth=1, payload=False):
     return out[:F * depth * nb], rec[:F * depth], summary[0]
 
 
-class DeviceRecords:
+class DeviceRecords(DeviceArray):
     """Device-resident `[aeth_rs_record]`; `.to_host()` -> structured array with `corrected` and `status`."""
 
-    def __init__(self, ctx, n):
-        self.ctx, self.n = ctx, int(n)
-        self.ptr = ctx.alloc(max(self.n, 1) * 8)
-
-    def __len__(self):
-        return self.n
-
-    def to_host(self):
-        out = np.zeros(self.n, RECORD)
-        if self.n:
-            self.ctx.download(self.ptr, out.view(np.uint8))
-        return out
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr); self.ptr = None
-        except Exception:
-            pass
+    DTYPE = RECORD
 
 
-class DeviceSummary:
+class DeviceSummary(DeviceArray):
     """Device-resident aeth_rs_summary; `.to_host()` waits and returns a record with `n_failed` and `n_corrected`."""
 
+    DTYPE = SUMMARY
+
     def __init__(self, ctx):
-        self.ctx = ctx
-        self.ptr = ctx.alloc(16)
+        super().__init__(ctx, 1)
 
     def to_host(self):
-        out = np.zeros(1, SUMMARY)
-        self.ctx.download(self.ptr, out.view(np.uint8))
-        return out[0]
-
-    def __del__(self):
-        try:
-            if self.ptr and self.ctx.h:
-                self.ctx.free(self.ptr); self.ptr = None
-        except Exception:
-            pass
+        return super().to_host()[0]
 
 
-class Rs:
+class Rs(Handle):
     """Rs(ctx, code_or_name): the object owns the field tables on the device."""
 
+    DESTROY = "aeth_rs_destroy"
+
     def __init__(self, ctx, code):
-        self.ctx = ctx
-        self._lib = _lib.load()
-        self.h = C.c_void_p()
+        super().__init__(ctx)
         self.code = _code(code)
         check(self._lib.aeth_rs_create(ctx.h, C.byref(self.code), C.byref(self.h)))
 
@@ -172,15 +147,3 @@ class Rs:
                                        PAYLOAD if payload else 0, C.c_void_p(out.ptr), out.n, C.c_void_p(rec.ptr) if rec is not None else None,
                                        C.c_void_p(summ.ptr) if summ is not None else None))
         return out, rec, summ
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            if self.ctx.h:                                           # a closed context has taken the stream with it
-                self._lib.aeth_rs_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
