@@ -329,6 +329,20 @@ PROTOTYPES = {
     "aeth_polar_lds_bytes": (sz, [vp]),
     "aeth_polar_encode": (i32, [vp, vp, sz, vp, sz]),
     "aeth_polar_decode": (i32, [vp, vp, sz, vp, C.c_uint32, vp, sz, vp]),
+    "aeth_turbo_named": (i32, [C.c_char_p, vp]),
+    "aeth_turbo_qpp": (i32, [C.c_uint32, C.c_uint32, C.c_uint32, vp, sz]),
+    "aeth_turbo_create": (i32, [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, pvp]),
+    "aeth_turbo_destroy": (i32, [vp]),
+    "aeth_turbo_k": (sz, [vp]),
+    "aeth_turbo_n": (sz, [vp]),
+    "aeth_turbo_states": (C.c_uint32, [vp]),
+    "aeth_turbo_window": (C.c_uint32, [vp]),
+    "aeth_turbo_warmup": (C.c_uint32, [vp]),
+    "aeth_turbo_windows": (C.c_uint32, [vp]),
+    "aeth_turbo_group": (C.c_uint32, [vp]),
+    "aeth_turbo_lds_bytes": (sz, [vp]),
+    "aeth_turbo_encode": (i32, [vp, vp, sz, vp, sz]),
+    "aeth_turbo_decode": (i32, [vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp]),
 }
 
 _lib = None

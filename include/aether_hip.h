@@ -59,6 +59,7 @@ typedef struct aeth_remap aeth_remap;   /* rate matching: a periodic byte map (p
 typedef struct aeth_crc aeth_crc;       /* frame checks: a CRC of width 1 .. 64 over bit frames: registers, attach, check */
 typedef struct aeth_rs aeth_rs;         /* Reed-Solomon code over GF(2^m): systematic encoder, errors-and-erasures decoder */
 typedef struct aeth_ldpc aeth_ldpc;     /* quasi-cyclic LDPC code: systematic encoder and layered integer min-sum decoder */
+typedef struct aeth_turbo aeth_turbo;   /* turbo code: two RSC encoders and a windowed max-log-MAP iterative decoder */
 typedef struct aeth_polar aeth_polar;   /* polar code: encoder and successive-cancellation decoder with a flip and candidate records */
 typedef struct aeth_ofdm aeth_ofdm;    /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
@@ -1419,6 +1420,85 @@ AETH_API size_t aeth_polar_lds_bytes(const aeth_polar *polar);     /* dynamic LD
 AETH_API int aeth_polar_encode(aeth_polar *polar, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded);
 AETH_API int aeth_polar_decode(aeth_polar *polar, const int8_t *soft_dev, size_t nsoft, const uint32_t *flip_dev, uint32_t flags,
                                uint8_t *bits_dev, size_t nbits, aeth_polar_record *rec_dev);
+
+/* ---- Turbo codes: RSC encoder, windowed max-log-MAP iterative decoder (no body in the reference) ---- */
+/* The channel code of the LTE and UMTS data channels and of CCSDS 131.0-B telemetry, behind aeth_demod_soft and aeth_remap
+ * and in front of aeth_crc_check.  Everything is integer arithmetic and defined byte for byte.  Bits are one byte per bit,
+ * taken & 1.  Soft values are int8_t; positive means bit 0 is likelier and 0 is an erasure.
+ *
+ * Constituent code.  Recursive systematic, constraint length 3 <= k <= 5, nu = k - 1, S = 2^nu states.  fb and ff are
+ * polynomials below 2^k with the current bit as the MSB (as in aeth_cc); fb must have bits k - 1 and 0 set, ff bit 0.
+ * State s holds a[t-1] at bit nu - 1 down to a[t-nu] at bit 0.  Step t with input u:
+ *     a = u ^ parity(s & fb & (S - 1));  reg = a 2^nu + s;  z = parity(reg & ff);  s' = reg >> 1.
+ * aeth_turbo_named knows "lte" (also UMTS: k = 4, fb = 013, ff = 015), "ccsds" (k = 5, fb = 023, ff = 033) and "k3"
+ * (k = 3, fb = 07, ff = 05, the test code).
+ *
+ * Encoder.  8 <= K <= 8192 information bits u and a permutation pi of K entries.  Encoder 1 runs on u[i], encoder 2 on
+ * u[pi[i]], both from state 0; each is then terminated by nu tail steps with u_tail = parity(s & fb & (S - 1)), which
+ * forces a = 0 and ends in state 0, and each tail step emits (u_tail, z).  A coded frame has N = 3 K + 4 nu bytes, planar:
+ *     [0, K) u;  [K, 2K) z of encoder 1;  [2K, 3K) z' of encoder 2;
+ *     3K + 2j, 3K + 2j + 1: tail (x, z) of encoder 1, j < nu;  3K + 2 nu + 2j, + 1: tail (x', z') of encoder 2.
+ * LTE's d0 / d1 / d2 order with its multiplexed tail is an aeth_remap table of period N.
+ *
+ * One soft-in soft-out pass siso(x, p).  x[t] (systematic plus a-priori) and p[t] (parity) are int32 for t < K + nu; all
+ * arithmetic is int32; NEG = -2^28.  The branch from s with input u carries g = (1 - 2u) x[t] + (1 - 2 z(s, u)) p[t].
+ * Forward and backward recursions take the max over the two branches into a state or out of it.  The K information steps
+ * are cut into windows [w W, min((w + 1) W, K)) with end e; window W and warm-up A are set at create.
+ *     Forward.   If w W - A <= 0 start at step 0 with alpha = {0, NEG, ...}, else at step w W - A with all states 0.
+ *     Backward.  If e + A >= K start at step K + nu with beta = {0, NEG, ...} and run back through the tail, else at step
+ *                e + A with all states 0.
+ *     Output.    D[t] = max_s(alpha_t[s] + g(0) + beta_{t+1}[s'(s, 0)]) - max_s(alpha_t[s] + g(1) + beta_{t+1}[s'(s, 1)]).
+ * W >= K, or A >= K, is the exact max-log-MAP of the terminated trellis.  Windows do not depend on each other, so the
+ * result does not depend on how a kernel distributes them.  Nothing overflows: |x| <= 128 + 2047, |p| <= 128, a path stays
+ * below 1.9e7, alpha + g + beta above -2^31 even with two sentinels, and both hypotheses are always finite.
+ *
+ * Iterations.  scale(e) = sign(e) min((3 |e|) >> 3, 2047).  Per codeword: systematic s[0 .. K), parities p1 and p2 each
+ * followed by its tail parities, tail systematics t1 and t2, a1 = 0.  Iteration i = 1 .. max_iter:
+ *     x1 = s + a1;  D1 = siso(x1 | t1, p1)  (tail steps carry no a-priori);  e1 = D1 - 2 x1;  a2[i] = scale(e1)[pi[i]];
+ *     x2[i] = s[pi[i]] + a2[i];  D2 = siso(x2 | t2, p2);  e2 = D2 - 2 x2;  a1[pi[i]] = scale(e2)[i];
+ *     h1 = D1 < 0;  h2[pi[i]] = D2[i] < 0  (zero decides bit 0);  disagreements = #{h1 != h2}.
+ * With AETH_TURBO_EARLY a codeword stops after an iteration with disagreements == 0.  The output is h2 of the last
+ * iteration run, K bytes per codeword; rec_dev (may be NULL, 4-byte aligned) receives {iterations run, disagreements after
+ * the last} per codeword.  Codewords are independent: a call cut at any codeword equals two calls byte for byte.
+ *
+ * aeth_turbo_qpp fills pi[i] = (f1 i + f2 i^2) mod K in 64-bit arithmetic (host, no context): K outside 8 .. 8192 and a
+ * result that is no permutation are AETH_E_ARG, count < K AETH_E_LEN; a refused call writes nothing.
+ *
+ * Refusals, each naming the value, before any device work.  Create: k outside 3 .. 5 (AETH_E_UNSUPPORTED); a bad fb or ff;
+ * K outside 8 .. 8192; window = 0 or warmup > 8192; pi NULL, an entry >= K or a repeated entry (naming index and value);
+ * more than 1024 windows per codeword (AETH_E_UNSUPPORTED).  Encode: nbits != F K or ncoded != F N (AETH_E_LEN).  Decode:
+ * max_iter outside 1 .. 64; unknown flag bits; nsoft != F N or nbits != F K (AETH_E_LEN); ranges that share a byte; a
+ * misaligned rec_dev (AETH_E_ALIGN); 2^31 or more workgroups of aeth_turbo_group codewords (AETH_E_UNSUPPORTED).  soft and
+ * bits may have any byte alignment; F = 0 launches nothing.  Getters return 0 for NULL, aeth_turbo_destroy(NULL) is
+ * AETH_OK.  All device calls are ordered on the context's stream and none waits.
+ *
+ * Kernel.  A lane owns one window with all S state metrics in registers; a workgroup owns aeth_turbo_group codewords on
+ * aeth_turbo_lds_bytes of dynamic LDS (the frame's soft values, the interleaved systematics and both a-priori arrays stay
+ * there for the whole call) and keeps the forward metrics of its windows as int32 in device memory the object owns,
+ * [step][state][lane].  The object also owns pi and its inverse on the device.
+ *
+ * Not built: soft posterior output; true log-MAP with a correction table; next-iteration initialisation of window edges;
+ * duo-binary (DVB-RCS) codes; K > 8192 (which rules out CCSDS K = 8920); the LTE (f1, f2) catalogue and sub-block rate
+ * matching; an aeth_stream_op kind and host-slice flavours. */
+#define AETH_TURBO_EARLY 1u
+typedef struct aeth_turbo_code { uint32_t k, fb, ff; } aeth_turbo_code;
+typedef struct aeth_turbo_record { uint32_t iterations, disagreements; } aeth_turbo_record;
+AETH_API int aeth_turbo_named(const char *name, aeth_turbo_code *code_out);
+AETH_API int aeth_turbo_qpp(uint32_t K, uint32_t f1, uint32_t f2, uint32_t *pi_out, size_t count);
+AETH_API int aeth_turbo_create(aeth_ctx *ctx, const aeth_turbo_code *code, uint32_t K, const uint32_t *pi_host, uint32_t window,
+                               uint32_t warmup, aeth_turbo **out);
+AETH_API int aeth_turbo_destroy(aeth_turbo *turbo);
+AETH_API size_t aeth_turbo_k(const aeth_turbo *turbo);             /* information bits of a codeword */
+AETH_API size_t aeth_turbo_n(const aeth_turbo *turbo);             /* coded bytes of a codeword, 3 K + 4 nu */
+AETH_API uint32_t aeth_turbo_states(const aeth_turbo *turbo);
+AETH_API uint32_t aeth_turbo_window(const aeth_turbo *turbo);
+AETH_API uint32_t aeth_turbo_warmup(const aeth_turbo *turbo);
+AETH_API uint32_t aeth_turbo_windows(const aeth_turbo *turbo);     /* windows, and decoder lanes, per codeword */
+AETH_API uint32_t aeth_turbo_group(const aeth_turbo *turbo);       /* codewords per decoder workgroup */
+AETH_API size_t aeth_turbo_lds_bytes(const aeth_turbo *turbo);     /* dynamic LDS of a decoder workgroup */
+AETH_API int aeth_turbo_encode(aeth_turbo *turbo, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded);
+AETH_API int aeth_turbo_decode(aeth_turbo *turbo, const int8_t *soft_dev, size_t nsoft, uint32_t max_iter, uint32_t flags, uint8_t *bits_dev,
+                               size_t nbits, aeth_turbo_record *rec_dev);
 
 /* ---- OFDM symbols (no body in the reference: it has Fft, VecOps::vec_mul and chunks_mut(fft_len) framing only) ---- */
 /* The framing and the one-tap equaliser of an OFDM link; everything else such a link needs is above (aeth_seq_scramble,

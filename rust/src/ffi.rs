@@ -34,6 +34,11 @@ pub const AETH_RS_PAYLOAD: u32 = 1;
 pub const AETH_POLAR_CODEWORD: u32 = 1; pub const AETH_POLAR_NONE: u32 = 0xFFFF_FFFF;
 /// aeth_polar_record: the four information leaves with the least (|L|, i), ascending; empty slots hold 0xFFFFFFFF
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_polar_record { pub index: [u32; 4], pub abs: [u32; 4] }
+#[repr(C)] pub struct aeth_turbo { _p: [u8; 0] }
+pub const AETH_TURBO_EARLY: u32 = 1;
+/// aeth_turbo_code: a recursive systematic constituent code, constraint length k, polynomials with the current bit as the MSB
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_turbo_code { pub k: u32, pub fb: u32, pub ff: u32 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_turbo_record { pub iterations: u32, pub disagreements: u32 }
 #[repr(C)] pub struct aeth_ofdm { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_event { _p: [u8; 0] }
 #[repr(C)] pub struct aeth_pool { _p: [u8; 0] }
@@ -421,6 +426,22 @@ extern "C" {
     pub fn aeth_polar_encode(polar: *mut aeth_polar, bits_dev: *const u8, nbits: usize, coded_dev: *mut u8, ncoded: usize) -> c_int;
     pub fn aeth_polar_decode(polar: *mut aeth_polar, soft_dev: *const i8, nsoft: usize, flip_dev: *const u32, flags: u32, bits_dev: *mut u8,
                              nbits: usize, rec_dev: *mut aeth_polar_record) -> c_int;
+    pub fn aeth_turbo_named(name: *const c_char, code_out: *mut aeth_turbo_code) -> c_int;
+    pub fn aeth_turbo_qpp(k: u32, f1: u32, f2: u32, pi_out: *mut u32, count: usize) -> c_int;
+    pub fn aeth_turbo_create(ctx: *mut aeth_ctx, code: *const aeth_turbo_code, k: u32, pi_host: *const u32, window: u32, warmup: u32,
+                             out: *mut *mut aeth_turbo) -> c_int;
+    pub fn aeth_turbo_destroy(turbo: *mut aeth_turbo) -> c_int;
+    pub fn aeth_turbo_k(turbo: *const aeth_turbo) -> usize;
+    pub fn aeth_turbo_n(turbo: *const aeth_turbo) -> usize;
+    pub fn aeth_turbo_states(turbo: *const aeth_turbo) -> u32;
+    pub fn aeth_turbo_window(turbo: *const aeth_turbo) -> u32;
+    pub fn aeth_turbo_warmup(turbo: *const aeth_turbo) -> u32;
+    pub fn aeth_turbo_windows(turbo: *const aeth_turbo) -> u32;
+    pub fn aeth_turbo_group(turbo: *const aeth_turbo) -> u32;
+    pub fn aeth_turbo_lds_bytes(turbo: *const aeth_turbo) -> usize;
+    pub fn aeth_turbo_encode(turbo: *mut aeth_turbo, bits_dev: *const u8, nbits: usize, coded_dev: *mut u8, ncoded: usize) -> c_int;
+    pub fn aeth_turbo_decode(turbo: *mut aeth_turbo, soft_dev: *const i8, nsoft: usize, max_iter: u32, flags: u32, bits_dev: *mut u8,
+                             nbits: usize, rec_dev: *mut aeth_turbo_record) -> c_int;
     pub fn aeth_pool_create(ctx: *mut aeth_ctx, elem_bytes: usize, initial_len: usize, flags: c_int, out: *mut *mut aeth_pool) -> c_int;
     pub fn aeth_pool_destroy(pool: *mut aeth_pool) -> c_int;
     pub fn aeth_pool_take(pool: *mut aeth_pool, buf: *mut *mut c_void) -> c_int;
