@@ -45,7 +45,7 @@ from .ldpc import Ldpc                                    # noqa: E402
 from . import rs                                          # noqa: E402
 from .rs import Rs                                        # noqa: E402
 from . import polar                                       # noqa: E402
-from .polar import Polar                                  # noqa: E402
+from .polar import Polar, PolarList                         # noqa: E402
 from . import turbo                                       # noqa: E402
 from .turbo import Turbo                                  # noqa: E402
 from . import ofdm                                        # noqa: E402
@@ -60,5 +60,5 @@ __all__ = ["AetherError", "LengthMismatch", "Context", "DeviceVec", "DeviceF32",
            "LEVEL_DB", "LEVEL_POWER_DB", "Scale", "HipFft",
            "SIGN_REF_FWD", "SIGN_REF_BWD", "Fir", "Corr", "CorrPeak", "sampling", "modulation", "noise", "sequence", "Sequence",
            "lte_gold", "chan", "Channelizer", "synth", "Synthesizer", "resamp", "Resampler", "arb", "ArbResampler", "step_word",
-           "nco", "Nco", "sync", "mov", "cc", "ConvCode", "remap", "Remap", "crc", "Crc", "DeviceU64", "pack_bits", "unpack_bits", "ldpc", "Ldpc", "rs", "Rs", "polar", "Polar", "turbo", "Turbo", "ofdm", "Ofdm", "DeviceBits", "DeviceSoft",
+           "nco", "Nco", "sync", "mov", "cc", "ConvCode", "remap", "Remap", "crc", "Crc", "DeviceU64", "pack_bits", "unpack_bits", "ldpc", "Ldpc", "rs", "Rs", "polar", "Polar", "PolarList", "turbo", "Turbo", "ofdm", "Ofdm", "DeviceBits", "DeviceSoft",
            "assert_evm", "evm_db"]

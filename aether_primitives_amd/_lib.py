@@ -329,6 +329,16 @@ PROTOTYPES = {
     "aeth_polar_lds_bytes": (sz, [vp]),
     "aeth_polar_encode": (i32, [vp, vp, sz, vp, sz]),
     "aeth_polar_decode": (i32, [vp, vp, sz, vp, C.c_uint32, vp, sz, vp]),
+    "aeth_polar_list_create": (i32, [vp, C.c_uint32, vp, C.c_uint32, pvp]),
+    "aeth_polar_list_destroy": (i32, [vp]),
+    "aeth_polar_list_n": (sz, [vp]),
+    "aeth_polar_list_k": (sz, [vp]),
+    "aeth_polar_list_paths": (C.c_uint32, [vp]),
+    "aeth_polar_list_lanes": (C.c_uint32, [vp]),
+    "aeth_polar_list_group": (C.c_uint32, [vp]),
+    "aeth_polar_list_lds_bytes": (sz, [vp]),
+    "aeth_polar_list_decode": (i32, [vp, vp, sz, C.c_uint32, vp, sz, vp]),
+    "aeth_polar_list_pick": (i32, [vp, vp, sz, sz, C.c_uint32, vp, vp, vp]),
     "aeth_turbo_named": (i32, [C.c_char_p, vp]),
     "aeth_turbo_qpp": (i32, [C.c_uint32, C.c_uint32, C.c_uint32, vp, sz]),
     "aeth_turbo_create": (i32, [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, pvp]),

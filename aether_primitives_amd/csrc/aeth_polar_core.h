@@ -81,6 +81,49 @@ inline void schedule(const uint8_t *mask, uint32_t lanes, uint32_t base, uint32_
     out.push_back(word(kJoin, lg, base, 0));
 }
 
+// ---- the list decoder (aeth_polar_list_*) ----
+constexpr uint32_t kMaxList = 8;
+
+inline int check_list(uint32_t L, uint32_t K)
+{
+    AETH_REQUIRE(L == 1 || L == 2 || L == 4 || L == 8, AETH_E_ARG, "L = %u: a list holds 1, 2, 4 or 8 paths", L);
+    AETH_REQUIRE(K >= 3 || (1u << K) >= L, AETH_E_ARG, "K = %u: the code has %u words, fewer than the L = %u paths", K, 1u << K, L);
+    return AETH_OK;
+}
+
+// lanes per path: not measured yet, so the largest T <= 16 with T L <= 64 and 2 T <= N
+inline uint32_t list_lanes(uint32_t n, uint32_t L)
+{
+    uint32_t T = 16;
+    while (T > 4 && (T * L > 64 || 2 * T > (1u << n))) T >>= 1;
+    return T;
+}
+
+// bytes of LDS per path: the levels of 2 T .. N / 2 int16 values and the packed partial sums, padded to 2 T modulo 128
+// so that the lanes of a half wave fall on distinct banks
+inline uint32_t list_stride(uint32_t n, uint32_t T)
+{
+    const uint32_t N = 1u << n, words = N > 32 ? N / 32 : 1;
+    const uint32_t raw = 2 * (N - 2 * T) + 4 * words;
+    return raw + ((2 * T + 128 - raw % 128) % 128);
+}
+
+// the list decoder's visits of the subtree (base, 2^lg): as `schedule`, but a wholly frozen child is visited too, because
+// its values add to the path metrics: its kF / kG word carries info = 0 and nothing below it follows.  A child of more
+// than `lanes` values that holds information carries info = 1.  No kZero: the frozen visit clears the child's bits.
+inline void list_schedule(const uint8_t *mask, uint32_t lanes, uint32_t base, uint32_t lg, std::vector<uint32_t> &out)
+{
+    const uint32_t m = 1u << lg, h = m >> 1;
+    const uint32_t halves[2] = {base, base + h};
+    for (uint32_t side = 0; side < 2; side++) {
+        const uint32_t b = halves[side];
+        const bool frozen = !any_info(mask, b, h);
+        out.push_back(word(side ? kG : kF, lg, base, frozen ? 0 : h == lanes ? bits_of(mask, b, h) : 1));
+        if (h > lanes && !frozen) list_schedule(mask, lanes, b, lg - 1, out);
+    }
+    out.push_back(word(kJoin, lg, base, 0));
+}
+
 // the encoder's position table: the rank of an information position among the information positions, 0xffff if frozen
 inline void positions(const uint8_t *mask, uint32_t N, std::vector<uint16_t> &tab, std::vector<uint16_t> &info)
 {

@@ -61,6 +61,7 @@ typedef struct aeth_rs aeth_rs;         /* Reed-Solomon code over GF(2^m): syste
 typedef struct aeth_ldpc aeth_ldpc;     /* quasi-cyclic LDPC code: systematic encoder and layered integer min-sum decoder */
 typedef struct aeth_turbo aeth_turbo;   /* turbo code: two RSC encoders and a windowed max-log-MAP iterative decoder */
 typedef struct aeth_polar aeth_polar;   /* polar code: encoder and successive-cancellation decoder with a flip and candidate records */
+typedef struct aeth_polar_list aeth_polar_list;   /* polar code: successive-cancellation list decoder with path metrics */
 typedef struct aeth_ofdm aeth_ofdm;    /* OFDM symbols: strip + transform + pick + equalise, and the way back, one kernel each */
 typedef struct aeth_event aeth_event;   /* hipEvent on the context's stream       */
 typedef struct aeth_pool aeth_pool;     /* replaces Pool<T> (src/pool.rs:71-160) for pinned host buffers */
@@ -1402,9 +1403,9 @@ AETH_API int aeth_rs_decode(aeth_rs *rs, const uint8_t *in_dev, size_t nin, cons
  * in LDS, those below live in registers and exchange across lanes; partial sums are packed bits; the tree walk is a
  * schedule built at create, wholly frozen subtrees pruned.
  *
- * Not built: list decoding (SCL); rate-1 / SPC / repetition node shortcuts (they skip the leaf values the record
- * needs); the 5G reliability sequence, sub-block interleaver and parity-check bits; systematic polar encoding; n > 10; an
- * aeth_stream_op kind and host-slice flavours. */
+ * Not built: rate-1 / SPC / repetition node shortcuts (they skip the leaf values the record needs); the 5G reliability
+ * sequence, sub-block interleaver and parity-check bits; systematic polar encoding; n > 10; an aeth_stream_op kind and
+ * host-slice flavours.  List decoding is aeth_polar_list below. */
 #define AETH_POLAR_CODEWORD 1u
 #define AETH_POLAR_NONE 0xFFFFFFFFu
 typedef struct aeth_polar_record { uint32_t index[4]; uint32_t abs[4]; } aeth_polar_record;
@@ -1420,6 +1421,70 @@ AETH_API size_t aeth_polar_lds_bytes(const aeth_polar *polar);     /* dynamic LD
 AETH_API int aeth_polar_encode(aeth_polar *polar, const uint8_t *bits_dev, size_t nbits, uint8_t *coded_dev, size_t ncoded);
 AETH_API int aeth_polar_decode(aeth_polar *polar, const int8_t *soft_dev, size_t nsoft, const uint32_t *flip_dev, uint32_t flags,
                                uint8_t *bits_dev, size_t nbits, aeth_polar_record *rec_dev);
+
+/* ---- Polar codes: successive-cancellation list decoder and the CRC's pick among its paths (no body in the reference) ---- */
+/* The decoder the 5G control channels are specified around: L paths per codeword, and a CRC that chooses among them on the
+ * device (aeth_crc_check over the F L rows, then aeth_polar_list_pick).  A handle of its own beside aeth_polar.  n, mask, N,
+ * K and the bit and soft conventions are exactly those of aeth_polar_create; L is 1, 2, 4 or 8 (else AETH_E_ARG), and
+ * 2^K < L is refused (AETH_E_ARG): the code has fewer words than paths.  Everything is integer arithmetic and defined byte
+ * for byte.
+ *
+ * State.  An ordered list of A paths, A = 1 at the start.  A path holds its decisions u[0..i) and a metric PM (uint32_t,
+ * 0 at the start).
+ *
+ * Leaf walk.  Leaves are taken in ascending i.  For path p, lambda_p is the value that dec of the SC definition above
+ * reaches at leaf i under that path's own earlier decisions: the same f and g, and nothing saturates.
+ *     frozen leaf: u_i = 0; PM_p += |lambda_p| if lambda_p < 0; the list order is unchanged.
+ *     information leaf: each (p, b), b in {0, 1}, is a candidate of metric PM_p + (|lambda_p| if b != (lambda_p < 0), else
+ *         0).  The candidates are sorted ascending by (metric, p, b); the first min(2 A, L) become the new list in that
+ *         order, each with u_i = b.
+ * Final order.  After leaf N - 1 the list is sorted once more by (PM, position); this matters when frozen leaves trail.
+ *
+ * Output.  Without AETH_POLAR_ALL path 0's K information decisions in ascending i, nbits = F K; with it all L paths in
+ * list order, nbits = F L K.  With AETH_POLAR_CODEWORD the N re-encoded bits x^ = transform(u) take the place of the K
+ * decisions.  Anything else is AETH_E_LEN.  Codewords are independent: a call cut at any codeword equals two calls byte
+ * for byte, and nothing depends on the grouping getters.
+ *
+ * Record.  rec_dev may be NULL; 4-byte aligned, one aeth_polar_list_record per codeword: metric[0..L) the final metrics,
+ * ascending, slots L .. 7 hold 0xFFFFFFFF.
+ *
+ * Two facts, both checked against a plain restatement (tests/polar_list_truth.py):
+ *   - L = 1 is aeth_polar_decode with flip = NULL, byte for byte.
+ *   - A finished path's metric equals sum over j of |soft_j| [x^_j != (soft_j < 0)] over its re-encoded codeword x^.
+ *     Hence PM <= 128 N <= 2^17, and the sort key metric 2 L + 2 p + b fits 32 bits.
+ * The same induction shows that a wholly frozen subtree adds sum over j of |v_j| [v_j < 0] over the node's own values
+ * v; the kernel uses that instead of walking the subtree, the restatement walks every leaf.
+ *
+ * aeth_polar_list_pick.  rows_dev holds F L rows of row_bytes bytes (the ALL output, or the payload aeth_crc_check
+ * stripped from it) and diff_dev that check's F L words.  Per codeword f: which[f] is the least r with diff[f L + r] == 0,
+ * else AETH_POLAR_NONE; out row f is row which[f] of the codeword, or row 0 when none passes.  One pass; any alignment for
+ * the bytes; diff_dev 8-byte and which_dev 4-byte aligned (else AETH_E_ALIGN); which_dev may be NULL.  1 <= L <= 8 here
+ * (else AETH_E_ARG), row_bytes = 0 is AETH_E_LEN and row_bytes > 2^30 AETH_E_UNSUPPORTED; F = 0 launches nothing.
+ *
+ * Refusals as for aeth_polar, each naming the value, before any device work; getters return 0 for NULL and
+ * aeth_polar_list_destroy(NULL) is AETH_OK.  All device calls are ordered on the context's stream and none waits.
+ *
+ * Kernel.  aeth_polar_list_lanes lanes share a path and lanes x paths <= 64 a codeword, which never leaves its wave; a
+ * workgroup is one wave of aeth_polar_list_group = 64 / (lanes paths) codewords on aeth_polar_list_lds_bytes of dynamic LDS.
+ * The paths walk one schedule in lockstep, each in the slot of its list position; a fork moves the registers and the packed
+ * partial sums, never a level.  lanes is the largest T <= 16 with T L <= 64 and 2 T <= N until it is measured.
+ *
+ * Not built: rate-1 / SPC / repetition node shortcuts; L > 8; the 5G sequence and parity-check bits; n > 10; an
+ * aeth_stream_op kind and host-slice flavours; a summary of the pick. */
+#define AETH_POLAR_ALL 2u
+typedef struct aeth_polar_list_record { uint32_t metric[8]; } aeth_polar_list_record;
+AETH_API int aeth_polar_list_create(aeth_ctx *ctx, uint32_t n, const uint8_t *mask, uint32_t L, aeth_polar_list **out);
+AETH_API int aeth_polar_list_destroy(aeth_polar_list *list);
+AETH_API size_t aeth_polar_list_n(const aeth_polar_list *list);
+AETH_API size_t aeth_polar_list_k(const aeth_polar_list *list);
+AETH_API uint32_t aeth_polar_list_paths(const aeth_polar_list *list);     /* L */
+AETH_API uint32_t aeth_polar_list_lanes(const aeth_polar_list *list);     /* lanes per path */
+AETH_API uint32_t aeth_polar_list_group(const aeth_polar_list *list);     /* codewords per workgroup */
+AETH_API size_t aeth_polar_list_lds_bytes(const aeth_polar_list *list);   /* dynamic LDS of a workgroup */
+AETH_API int aeth_polar_list_decode(aeth_polar_list *list, const int8_t *soft_dev, size_t nsoft, uint32_t flags, uint8_t *bits_dev,
+                                    size_t nbits, aeth_polar_list_record *rec_dev);
+AETH_API int aeth_polar_list_pick(aeth_ctx *ctx, const uint8_t *rows_dev, size_t row_bytes, size_t F, uint32_t L, const uint64_t *diff_dev,
+                                  uint8_t *out_dev, uint32_t *which_dev);
 
 /* ---- Turbo codes: RSC encoder, windowed max-log-MAP iterative decoder (no body in the reference) ---- */
 /* The channel code of the LTE and UMTS data channels and of CCSDS 131.0-B telemetry, behind aeth_demod_soft and aeth_remap

@@ -31,9 +31,12 @@ pub const AETH_RS_PAYLOAD: u32 = 1;
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_rs_record { pub corrected: u32, pub status: u32 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_rs_summary { pub n_failed: u64, pub n_corrected: u64 }
 #[repr(C)] pub struct aeth_polar { _p: [u8; 0] }
+#[repr(C)] pub struct aeth_polar_list { _p: [u8; 0] }
 pub const AETH_POLAR_CODEWORD: u32 = 1; pub const AETH_POLAR_NONE: u32 = 0xFFFF_FFFF;
 /// aeth_polar_record: the four information leaves with the least (|L|, i), ascending; empty slots hold 0xFFFFFFFF
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_polar_record { pub index: [u32; 4], pub abs: [u32; 4] }
+/// aeth_polar_list_record: the final metrics of the L paths, ascending; slots L .. 7 hold 0xFFFFFFFF
+#[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)] pub struct aeth_polar_list_record { pub metric: [u32; 8] }
 #[repr(C)] pub struct aeth_turbo { _p: [u8; 0] }
 pub const AETH_TURBO_EARLY: u32 = 1;
 /// aeth_turbo_code: a recursive systematic constituent code, constraint length k, polynomials with the current bit as the MSB
@@ -426,6 +429,18 @@ extern "C" {
     pub fn aeth_polar_encode(polar: *mut aeth_polar, bits_dev: *const u8, nbits: usize, coded_dev: *mut u8, ncoded: usize) -> c_int;
     pub fn aeth_polar_decode(polar: *mut aeth_polar, soft_dev: *const i8, nsoft: usize, flip_dev: *const u32, flags: u32, bits_dev: *mut u8,
                              nbits: usize, rec_dev: *mut aeth_polar_record) -> c_int;
+    pub fn aeth_polar_list_create(ctx: *mut aeth_ctx, n: u32, mask: *const u8, l: u32, out: *mut *mut aeth_polar_list) -> c_int;
+    pub fn aeth_polar_list_destroy(list: *mut aeth_polar_list) -> c_int;
+    pub fn aeth_polar_list_n(list: *const aeth_polar_list) -> usize;
+    pub fn aeth_polar_list_k(list: *const aeth_polar_list) -> usize;
+    pub fn aeth_polar_list_paths(list: *const aeth_polar_list) -> u32;
+    pub fn aeth_polar_list_lanes(list: *const aeth_polar_list) -> u32;
+    pub fn aeth_polar_list_group(list: *const aeth_polar_list) -> u32;
+    pub fn aeth_polar_list_lds_bytes(list: *const aeth_polar_list) -> usize;
+    pub fn aeth_polar_list_decode(list: *mut aeth_polar_list, soft_dev: *const i8, nsoft: usize, flags: u32, bits_dev: *mut u8, nbits: usize,
+                                  rec_dev: *mut aeth_polar_list_record) -> c_int;
+    pub fn aeth_polar_list_pick(ctx: *mut aeth_ctx, rows_dev: *const u8, row_bytes: usize, f: usize, l: u32, diff_dev: *const u64,
+                                out_dev: *mut u8, which_dev: *mut u32) -> c_int;
     pub fn aeth_turbo_named(name: *const c_char, code_out: *mut aeth_turbo_code) -> c_int;
     pub fn aeth_turbo_qpp(k: u32, f1: u32, f2: u32, pi_out: *mut u32, count: usize) -> c_int;
     pub fn aeth_turbo_create(ctx: *mut aeth_ctx, code: *const aeth_turbo_code, k: u32, pi_host: *const u32, window: u32, warmup: u32,
